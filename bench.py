@@ -6,7 +6,11 @@ in HBM: zero_grad -> CloudEmbedder.run (PointNet) -> model.ecc (filter MLP + 10 
 weighted cross entropy -> backward -> bw_hook (PointNet backward) -> [N>1: ONE flat-bucket RCCL all-reduce]
 -> element-wise gradient clamp -> Adam step      (the reference's trainer window, learning/main.py:199-213).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+A plain run sets up, warms up (W steps), times exactly K steps, checks the run and prints the line (ms_per_step = the K steps'
+wall time / K).  --full adds every side measurement (per-step event times, roofline, sustained repeat, trainer window,
+forward-only, CPU baseline, the other BASELINE.json configurations).  --dump-outputs DIR writes what the last timed step
+computed as DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments compare output for output.
 For N > 1 one rank per GPU: either the caller launches it with torch.distributed.run (RANK/LOCAL_RANK/WORLD_SIZE in the
 environment) or -- a plain `python bench.py --gpus N` without WORLD_SIZE -- the script re-launches ITSELF under
 torch.distributed.run with N ranks on 127.0.0.1 (it refuses when the node has fewer than N GPUs).  Every rank holds its
@@ -47,6 +51,27 @@ def make_batch(seeds, n_sp, n_edges, n_feat=14, n_classes=13):
     scenes = [synth.scene(s, n_sp=n_sp, n_edges=n_edges, n_feat=n_feat, n_classes=n_classes) for s in seeds]
     targets, GIs, (meta, flag, clouds, diam) = spg.eccpc_collate([spg.sample_from_scene(s, f'scene{i}') for i, s in enumerate(scenes)])
     return targets, GIs, flag, clouds, diam, scenes
+
+
+DUMP_MAX_ELEMENTS = 3 << 20      # per array (12 MB of float32): the five arrays of --dump-outputs stay below 64 MB
+
+
+def dump_outputs(path, exchange, arena, model):
+    """--dump-outputs: what the timed step handed back in its last step -- the loss and the logits it returns, the gradients it
+    left in the arena, the parameters after the optimiser update and the model's floating-point buffers (BatchNorm running
+    statistics) -- as float32 DIR/<name>.npy.  An array above DUMP_MAX_ELEMENTS is replaced by a fixed sample of its flattened
+    elements (ascending positions drawn by a generator seeded with 0: they depend on the array's size only), so that two builds
+    of the project compare element for element."""
+    torch.cuda.synchronize()
+    bufs = [b.detach().reshape(-1).float() for _, b in model.named_buffers() if b.is_floating_point()]
+    arrays = {'loss': exchange['loss'], 'logits': exchange['logits'], 'grads': arena.flat.grad, 'params': arena.flat.data,
+              'buffers': torch.cat(bufs) if bufs else torch.zeros(0)}
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_MAX_ELEMENTS:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMENTS, replace=False))]
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def cpu_model():
@@ -137,7 +162,7 @@ def gemm_traffic_live(args, log):
         for counter in ('FETCH_SIZE', 'WRITE_SIZE'):
             out = tempfile.mkdtemp(prefix=f'spg_pmc_{counter}_', dir='/tmp')
             cmd = [exe, '--kernel-trace', '--pmc', counter, '--output-format', 'rocpd', '-d', out, '--', sys.executable, os.path.abspath(__file__),
-                   '--steps', '4', '--warmup', '2', '--no-cpu-baseline', '--no-forward-only', '--no-trainer-window', '--no-roofline', '--no-extras',
+                   '--full', '--steps', '4', '--warmup', '2', '--no-cpu-baseline', '--no-forward-only', '--no-trainer-window', '--no-roofline', '--no-extras',
                    '--fused-step', str(args.fused_step),
                    '--precision', args.precision, '--scenes', str(args.scenes), '--n-sp', str(args.n_sp), '--n-edges', str(args.n_edges),
                    '--n-feat', str(args.n_feat), '--model-config', args.model_config]
@@ -277,7 +302,7 @@ def other_workloads(args, log):
     Semantic3D scale (10 000 superpoints, 50 000 superedges, 11 point features, vector filters `gru_10,f_8`) in fp32 and with
     the opt-in split-bf16 MFMA operands.  -> {name: {superpoints_per_s, ms_per_step, roofline fractions, ...}}"""
     import subprocess
-    common = ['--steps', '12', '--warmup', '4', '--no-cpu-baseline', '--no-forward-only', '--no-trainer-window', '--no-live-pmc',
+    common = ['--full', '--steps', '12', '--warmup', '4', '--no-cpu-baseline', '--no-forward-only', '--no-trainer-window', '--no-live-pmc',
               '--no-extras', '--fused-step', str(args.fused_step)]
     sema = ['--n-sp', '10000', '--n-edges', '50000', '--n-feat', '11', '--model-config', 'gru_10,f_8']
     runs = {'s3dis_2_scenes_per_step_f32': ['--scenes', '2'], 's3dis_8_scenes_per_step_f32': ['--scenes', '8'],
@@ -426,7 +451,15 @@ def main():
     ap.add_argument('--fused-step', type=int, default=1, help='1 (default): forward + backward as ONE library call (superpoint_graph_amd/fused.py: spg_train_step; same kernels and results as the module path, tests/test_gpu_fused.py); 0: CloudEmbedder.run -> model.ecc -> cross_entropy -> backward -> bw_hook through the modules')
     ap.add_argument('--infer-line', action='store_true', help='also time the evaluation forward of this run\'s model as one call (spg_infer_step) and report it with its roofline (`inference`)')
     ap.add_argument('--no-extras', action='store_true', help='skip the short runs of the other BASELINE.json configurations (2 / 8 scenes per step, Semantic3D scale in f32 and split-bf16) and the sustained repeat')
+    ap.add_argument('--full', action='store_true', help='also run everything besides the headline: per-step event times, the roofline (instrumented '
+                    'pass, live PMC passes), the sustained repeat, host enqueue, trainer window, forward-only, CPU baseline, the other '
+                    'BASELINE.json configurations and (N > 1) the all-reduce pass; the --no-* flags above switch parts of it off.  Without '
+                    '--full a run sets up, warms up, times the K steps, checks the run and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps, write what the timed step computed in its last '
+                    'step (loss, logits, gradients, updated parameters and BatchNorm statistics) as DIR/<name>.npy, float32 (rank 0)')
     args = ap.parse_args()
+    if not args.full:      # a plain run: the headline only
+        args.no_roofline = args.no_live_pmc = args.no_cpu_baseline = args.no_trainer_window = args.no_forward_only = args.no_extras = True
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         raise SystemExit(self_launch(args))
 
@@ -498,7 +531,7 @@ def main():
     def fwd_bwd():
         arena.zero_grad()
         if fstep is not None:      # the same step as ONE call into the library (include/spg_hip.h: spg_train_step)
-            exchange['loss'], _ = fstep(flag, clouds_d, diam_d, GIs[0], label_mode)
+            exchange['loss'], exchange['logits'] = fstep(flag, clouds_d, diam_d, GIs[0], label_mode)
             exchange['w'] = fstep.normaliser
             return
         emb = embedder.run(model, None, flag, clouds_d, diam_d)
@@ -509,7 +542,7 @@ def main():
             loss, exchange['w'] = ops.cross_entropy(out, label_mode, reduction='sum', return_normaliser=True)
         else:
             loss = ops.cross_entropy(out, label_mode)    # learning/main.py:205, one launch each way
-        exchange['loss'] = loss.detach()
+        exchange['loss'], exchange['logits'] = loss.detach(), out.detach()
         loss.backward(arena.one)                         # (a cached 1: autograd's implicit ones_like(loss) is a fill launch)
         embedder.bw_hook()
 
@@ -597,14 +630,17 @@ def main():
     # per-step device times (min / median / max next to the mean): the same K steps with one event pair per step.  This pass runs
     # FIRST (round 6): with the driver's W = 5 / K = 20 the timed region used to start 6 ms after a second of host-side set-up, on a
     # device whose clocks were still coming up -- the mean of the region sat 0.6-2.5 % above the median of this pass and above the
-    # sustained figure of the same run.  The order changes nothing in what is timed below.
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
-    ev[0].record()
-    for i in range(args.steps):
-        step()
-        ev[i + 1].record()
-    barrier()
-    step_ms = sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(args.steps))
+    # sustained figure of the same run.  The order changes nothing in what is timed below.  (--full only: a plain run times the K
+    # steps right after the warm-up.)
+    step_ms = None
+    if args.full:
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+        ev[0].record()
+        for i in range(args.steps):
+            step()
+            ev[i + 1].record()
+        barrier()
+        step_ms = sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(args.steps))
     t0 = time.perf_counter()
     for i in range(args.steps):
         step()
@@ -617,6 +653,9 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     value = n_sp_step * world * args.steps / dt
     log(f'timed region done: {ms_per_step:.3f} ms/step')
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, exchange, arena, model)
+        log(f'outputs of the last timed step written to {args.dump_outputs}')
 
     # who took part: every rank contributes 1 (all-reduce on the bench's process group) -- the line says how many ranks the
     # collectives actually saw, not what --gpus asked for
@@ -627,7 +666,7 @@ def main():
         ranks_seen = int(t.item())
     # the gradient exchange alone, event-bracketed on the compute stream in a short pass OUTSIDE the timed region
     ar_us = None
-    if dp:
+    if dp and args.full:
         e0 = [torch.cuda.Event(enable_timing=True) for _ in range(8)]
         e1 = [torch.cuda.Event(enable_timing=True) for _ in range(8)]
         for i in range(8):
@@ -663,7 +702,7 @@ def main():
     result = {
         'metric': 'superpoints/sec (embed+ECC fwd+bwd), S3DIS-shaped SPG', 'value': value, 'unit': 'superpoints/s',
         'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': ms_per_step,
-        'ms_per_step_min': step_ms[0], 'ms_per_step_median': step_ms[len(step_ms) // 2], 'ms_per_step_max': step_ms[-1],
+        **({'ms_per_step_min': step_ms[0], 'ms_per_step_median': step_ms[len(step_ms) // 2], 'ms_per_step_max': step_ms[-1]} if step_ms else {}),
         'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': {'f32': 'f32', 'bf16x3': 'bf16x3 (split-bf16 MFMA operands of the wide row-GEMMs, f32 accumulate and f32 everywhere else; NOT the headline arithmetic)', 'bf16': 'bf16 (MFMA operands of the wide row-GEMMs, f32 accumulate and f32 everywhere else; NOT the headline arithmetic)'}[args.precision], 'data': 'synthetic',
         'config': {'workload': wl,
                    'workload_detail': f'synthetic S3DIS-shaped SPG (SURVEY.md 8d scene(seed)): PointNet + {args.model_config}' + (' = S3DIS production model, matrix filters, 10 GRU iterations' if args.model_config == 'gru_10_0,f_13' else '') + '; one step = zero_grad, forward, weighted CE, backward, bw_hook, clamp + Adam on resident inputs',
@@ -821,7 +860,7 @@ def main():
             if 'roofline' in result and result['roofline'].get('traffic_source') != 'live':
                 result['roofline']['traffic_note'] = 'n_gpus>1: no live PMC passes; HBM bytes come from the N=1 run / the committed file'
         else:
-            result['cpu_baseline'] = {'skipped': '--no-cpu-baseline'}
+            result['cpu_baseline'] = {'skipped': '--no-cpu-baseline' if args.full else 'measured with --full only'}
         if world == 1 and not args.no_extras:
             ow = other_workloads(args, log)
             result['other_workloads'] = ow

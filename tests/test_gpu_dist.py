@@ -147,7 +147,7 @@ def test_bench_two_ranks_with_roofline_pass(hip):
     root = os.path.dirname(HERE)
     port = _free_port()
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
-           '--master-port', str(port), os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '2',
+           '--master-port', str(port), os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '2', '--full',
            '--backend', 'gloo', '--device-index', '0', '--n-sp', '200', '--n-edges', '800']
     out = subprocess.run(cmd, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0'), capture_output=True, text=True, timeout=400)
     assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
@@ -168,7 +168,7 @@ def test_bench_two_ranks_control_flow(hip, sync_bn, launcher):
     to start its own ranks (that command used to print an N = 1 line)."""
     import json
     root = os.path.dirname(HERE)
-    tail = [os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '2',
+    tail = [os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '2', '--full',
             '--backend', 'gloo', '--device-index', '0', '--sync-bn', str(sync_bn), '--no-cpu-baseline', '--no-forward-only', '--no-roofline']
     if launcher == 'torchrun':
         cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',

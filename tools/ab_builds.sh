@@ -6,7 +6,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 B="$1"; N=${2:-3}; shift; shift
 for i in $(seq $N); do
   for L in "" "$B"; do
-    SPG_HIP_LIB="$L" python $ROOT/bench.py "$@" --steps 40 --warmup 10 --no-cpu-baseline --no-forward-only --no-trainer-window --no-roofline --no-extras 2>/dev/null | python -c "
+    SPG_HIP_LIB="$L" python $ROOT/bench.py "$@" --steps 40 --warmup 10 --full --no-cpu-baseline --no-forward-only --no-trainer-window --no-roofline --no-extras 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('lib=[${L:-in-tree}]', round(d['ms_per_step'],4), 'min', round(d['ms_per_step_min'],4), 'median', round(d['ms_per_step_median'],4))"
   done
 done

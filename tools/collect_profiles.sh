@@ -1,7 +1,7 @@
 #!/bin/bash
 # Everything the round's measurement deliverables need, in one GPU-box call (run from the repo root):
 #   tools/collect_profiles.sh <tag>            e.g. r03  ->  gpurun_out/<tag>_{bench.json,kernel_stats.txt,pmc_*.txt,gemm_traffic.json}
-# Passes: (1) bench.py (default flags: the driver's command), (2) rocprofv3 --kernel-trace of the train steps, summarised
+# Passes: (1) bench.py --full (the headline and every side measurement), (2) rocprofv3 --kernel-trace of the train steps, summarised
 # over the steady-state window (tools/prof_summary.py), (3)+(4) --pmc FETCH_SIZE / --pmc WRITE_SIZE in separate passes
 # (never with other trace domains), each followed by the known-byte-count calibration of tools/pmc_calib.py.
 set -u
@@ -10,10 +10,10 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-STEPS="--no-cpu-baseline --no-forward-only --no-trainer-window --no-roofline --no-extras"
+STEPS="--full --no-cpu-baseline --no-forward-only --no-trainer-window --no-roofline --no-extras"
 db() { find $1 -name '*.db' | head -1; }
 
-timeout 900 python $ROOT/bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+timeout 900 python $ROOT/bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 tail -c 1500 $OUT/${TAG}_bench.err
 python - <<EOF2
 import json

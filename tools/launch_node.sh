@@ -11,7 +11,7 @@ set -euo pipefail
 cd "$(dirname "$0")/.."
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 N="${1:-8}"; SYNC="${2:-0}"; shift $(( $# > 2 ? 2 : $# )) || true
-SIDE="--no-forward-only --no-cpu-baseline --no-trainer-window --no-extras --no-live-pmc"
+SIDE="--full --no-forward-only --no-cpu-baseline --no-trainer-window --no-extras --no-live-pmc"
 run() {
   local n="$1"; shift
   if [ "$n" -eq 1 ]; then

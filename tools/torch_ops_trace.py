@@ -1,7 +1,7 @@
 import os, sys, types
 from collections import Counter
 import torch
-sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo'))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from superpoint_graph_amd import ops
 from superpoint_graph_amd.flat import FlatParameters
