@@ -461,15 +461,12 @@ int spg_prof_read_shapes(int* keys, double* vals, int max);
  * operand pair, ~2^-16 per product), 1 = bf16 operands; fp32 accumulation and fp32 tensors in every mode (tolerances:
  * tests/test_gpu_precision.py); key 8: 1 = run the GRU recurrence of spg_eccrnn_forward / _backward as one launch per
  * iteration instead of the persistent dataflow-synchronised launch (A/B timing and the equality test; the two forms give
- * bit-identical results), 2 = only the iteration-major form for more nodes than wavefronts (round 5) is off; key 9: 1 = the recurrent cell's parameter-gradient launches of spg_eccrnn_backward go to a
- * library-owned side stream next to the filter network's backward chain (experiment; measured slower, off by default).
+ * bit-identical results), 2 = only the iteration-major form for more nodes than wavefronts (round 5) is off.
  * key 10: 1 = train-mode BatchNorm statistics of spg_pointnet_forward go through per-workgroup partials and a finalize launch
  * per layer (the pre-round-3 path, still used with synchronised BatchNorm) instead of fixed-point slots finished by the
  * consuming GEMM.  key 11: 1 = no grouped launches (round 4: mutually independent few-row GEMMs / small reductions leave as
  * jobs of ONE kernel; the bodies are unchanged, results bit-identical -- A/B timing and the equality test).
- * key 12: 1 = few-row GEMMs with a reduction of >= 128 run in the split-K form (a 32 x 32 tile per workgroup, the four waves
- * split the reduction chunks; an experiment: measured no faster, off by default).
- * key 13: 1 = the masked (incomplete-tile) forward pipelines store scalars instead of vectors.  key 14: 1 = the backward of the
+ * key 14: 1 = the backward of the
  * 64- / 128-input-channel convolutions runs as separate data-gradient and weight-gradient launches instead of the fused
  * one-pass kernel (same arithmetic per element, different summation order of dW and of the BatchNorm-backward sums).
  * key 15: 1 = spg_train_step runs the classifier and the cross entropy as separate launches instead of inside the one-launch
@@ -477,11 +474,6 @@ int spg_prof_read_shapes(int* keys, double* vals, int max);
  * sequential fma chains instead of MFMA chunks: differences at fp32 round-off).  key 6: 1 = with the classifier inside the
  * recurrence, its weight / bias gradient leaves as a job of a grouped launch (+10 us) instead of being formed by service
  * workgroups of the persistent backward launch on the CUs the recurrence leaves idle.
- * key 16: 1 = spg_pointnet_backward hands the weight gradients of the pooled and of the first convolution to later launches as
- * LEAVES (round 5 experiment, OFF by default: slices of those launches -- row ranges of their split plan, same body, same plan:
- * results bit-identical -- travel next to the STN head's grouped launches instead of standing in front of the data gradients;
- * measured +29 us per step: a workgroup of the pooled layer's weight gradient runs ~60-90 us whatever the slice, the head's
- * launches are ~20 us each and already filled by the riding reductions -- DESIGN 4.16).
  * key 17: 1 = spg_pointnet_forward runs the first two convolutions of a segment (cloud -> 64 -> 64) as two row-GEMM launches
  * instead of the one-pass kernel of round 5 (spg_narrow.hip: first-layer statistics from the Gram matrix of the input, one
  * wavefront per block of 32 points through both layers; same MFMA order per element, the first layer's statistics exact instead
@@ -490,10 +482,6 @@ int spg_prof_read_shapes(int* keys, double* vals, int max);
  * gradient + spg_stn_dT instead of the one-pass kernel of round 5 (spg_narrow.hip: the layer's raw output is linear in the cloud,
  * so its part of the BatchNorm-backward formula collapses onto the Gram matrix -- one pass over the incoming gradient and the
  * cloud; results agree at fp32 round-off, tests/test_gpu_narrow.py).
- * key 19: 1 = the jobs of a grouped launch are ordered by workgroup length alone, as in round 4.  Default (round 5): the group's OWN
- * jobs -- what the next launch of the stream waits for -- take the first workgroup slots, riders / riding reductions / leaves
- * follow (bit-identical; -8.6 us per step: the job spans of an attribution build showed the FC head's data gradient starting 17 us
- * into a 42 us launch, behind 581 riding weight-gradient workgroups; bench.py --group-trace).
  * key 20: > 0 = a spin bound for the waits of the one-launch recurrences below the built-in one (tests only: tests/test_gpu_failsafe.py
  * forces a time-out with it); -1 = every wait reports a time-out at once, whether its data had arrived or not (deterministic on the
  * smallest graphs: tests/test_gpu_main.py); 0 (default) = the built-in bound.
@@ -502,7 +490,9 @@ int spg_prof_read_shapes(int* keys, double* vals, int max);
  * key 22: 1 = the pooled convolution of a PointNet segment with 128 -> 256 channels keeps its separate weight-gradient and
  * data-gradient launches (+ finalize); default (round 6): the fused backward pair as two launches over the halves of its output
  * channels (spg_gemm.hip: spg_queue_bwdpair; 196 -> 167 us on the unit scene; results agree at fp32 round-off, tests/test_gpu_bwdpair.py).
- * Returns the previous value, -1 for an unknown key. */
+ * Keys 9, 12, 13, 16 and 19 are retired (side stream, split-K few-row GEMMs, scalar stores in the masked pipelines, weight-gradient
+ * leaves, round-4 job order: measured slower or settled, their code removed -- DESIGN.md); they accept only 0.
+ * Returns the previous value, -1 for an unknown key or a value the key does not accept. */
 int spg_tune(int key, int value);
 /* ------------------------------------------------------------------------------------------------
  * One training step's forward AND backward in ONE call (round 4): CloudEmbedder.run -> model.ecc (RNN-ECC module +

@@ -81,6 +81,8 @@ static int spg_num_cus() {
 int spg_tune_get(int key) { return (key >= 0 && key < SPG_TUNE_COUNT) ? g_tune[key] : 0; }
 extern "C" int spg_tune(int key, int value) {
   if (key < 0 || key >= SPG_TUNE_COUNT) return -1;
+  // retired keys: their code paths were measured slower or settled and are gone (include/spg_hip.h); only 0 is accepted
+  if ((key == 9 || key == 12 || key == 13 || key == 16 || key == 19) && value != 0) return -1;
 #ifndef SPG_ATTRIBUTION
   if ((key == SPG_TUNE_DBG || key == SPG_TUNE_NO_STAT_ACCUM) && value != 0) return -1;      // not in the production build
 #endif
@@ -165,7 +167,8 @@ struct SpgSmallJob {            // column sums: src [M, ld] -> dst [slices][N] (
 };
 // Kernel arguments of a grouped launch (<= 4 KiB): a table of job headers in launch order + the jobs' parameter structs packed
 // back to back (16-byte aligned) in one byte arena -- 12 small jobs or e.g. 2 row-GEMMs + 4 weight gradients + 4 small ones.
-struct SpgJobHdr { int kind, variant, gx, gy, gz, offset, weight, bx0; };      // bx0: first x index of the job's grid (a SLICE of a larger launch)
+// (`reserved` keeps the header at 32 bytes: spg_multi_body fetches the table -- the first 592 bytes of SpgMultiArgs -- in one batch)
+struct SpgJobHdr { int kind, variant, gx, gy, gz, offset, weight, reserved; };
 #define SPG_GROUP_MAX_JOBS 16
 #define SPG_GROUP_ARENA_BYTES 3440
 #define SPG_GROUP_MAX_WGRAD_ROWS 65536      // weight gradients over more rows than this are never grouped
@@ -190,10 +193,6 @@ constexpr int spg_gemm_variant(bool wred, int amode, bool full) {
 // A group is launched with the light build unless one of its jobs is a heavy variant (register counts of the stand-alone
 // instantiations, -Rpass-analysis=kernel-resource-usage).
 constexpr bool spg_gemm_variant_light(int v) { return v != 8; }      // 8 = data gradient, BNBWD prologue, full tiles: 144 VGPRs
-// split-K few-row bodies spg_fewrow_sk_body<WRED, AMODE>: ids 10 .. 13
-constexpr int spg_gemm_sk_variant(bool wred, int amode) {
-  return amode == SPG_PRO_IDENT ? (wred ? 12 : 10) : ((!wred && amode == SPG_PRO_AFFINE) ? 11 : ((wred && amode == SPG_PRO_BNBWD) ? 13 : -1));
-}
 // weight-gradient bodies the group can run (the shapes the few-row layers of the S3DIS / Semantic3D configurations produce)
 //   X(id, IT, JT, WI, WJ, AMODE, BMODE, FULL, COLSUM, LIGHT)
 #define SPG_WGRAD_VARIANTS(X)                                                                                    \
@@ -207,10 +206,7 @@ constexpr int spg_gemm_sk_variant(bool wred, int amode) {
   X(12, 128, 32, 4, 1, 0, 1, false, true, false)    X(13, 128, 32, 4, 1, 0, 1, true, true, false)                \
   X(14, 64, 64, 2, 2, 0, 1, false, false, true)     X(15, 64, 64, 2, 2, 0, 1, true, false, true)                 \
   X(16, 128, 128, 2, 2, 0, 1, false, true, false)   X(17, 128, 128, 2, 2, 0, 1, true, true, false)               \
-  X(18, 128, 64, 2, 2, 3, 1, false, false, false)   X(19, 128, 64, 2, 2, 3, 1, true, false, false)               \
-  /* leaves of PointNet's backward that travel in slices next to the STN head's launches (spg_gemm.h: spg_leaf_*): the      \
-     pooled convolution's weight gradient (max-pool scatter x affine) and the first convolution's (BatchNorm-backward x cloud) */ \
-  X(20, 128, 128, 2, 2, 4, 1, true, false, false)   X(21, 128, 32, 4, 1, 3, 2, false, false, false)
+  X(18, 128, 64, 2, 2, 3, 1, false, false, false)   X(19, 128, 64, 2, 2, 3, 1, true, false, false)
 constexpr int spg_wgrad_variant(int it, int jt, int amode, int bmode, bool full, bool colsum) {
 #define SPG_X(id, IT_, JT_, WI_, WJ_, AM_, BM_, FU_, CS_, LI_) \
   if (it == IT_ && jt == JT_ && amode == AM_ && bmode == BM_ && full == FU_ && colsum == CS_) return id;
@@ -227,7 +223,7 @@ constexpr bool spg_wgrad_variant_light(int v) {
 // host side (end of this file): true = the job was taken by the group that is open on this thread
 static bool spg_group_accepts(hipStream_t stream);
 static bool spg_group_add(int kind, int variant, const void* params, size_t bytes, dim3 grid, size_t lds, double flops, hipStream_t stream, int weight,
-                          std::function<int()> direct = nullptr, int bx0 = 0);
+                          std::function<int()> direct = nullptr);
 
 // ---------------------------------------------------------------------------------------------
 // forward / data-gradient kernel
@@ -1137,96 +1133,6 @@ __global__ __launch_bounds__(SPG_THREADS, 2) void spg_rowgemm_kernel(const SpgGe
 // ---------------------------------------------------------------------------------------------
 // few-row GEMM with the REDUCTION split over the four waves (round 4)
 // ---------------------------------------------------------------------------------------------
-// The FC layers over superpoints / edges (M = 1000 ... 5000 rows) are dependent chains of launches whose length is the length
-// of ONE workgroup's reduction: with the 32 x 128 tile above every wave owns 32 output columns and walks ALL K / 32 chunks
-// (~0.75 us each: 16 MFMAs + LDS staging + a barrier) -- PointNet's 257 -> 256 layer 9 chunks, the classifier 11, the filter
-// network's last data gradient (K = 1024) 32: a 24 us launch for 0.6 GFLOP.  Here a workgroup owns a 32 x 32 output tile and its
-// four waves split the CHUNKS (wave w takes chunks w, w + 4, ...): the chain is 4x shorter and there are 4x as many workgroups
-// (N / 32 column tiles); no LDS staging and no barrier in the loop -- a lane loads its MFMA operands straight from global memory
-// (lane (r, h) owns row r / output column r and the 16 reduction indices 16h .. 16h + 15 of the chunk: four 16-byte loads per
-// operand) and applies the operand prologue in registers; the four partial accumulators are summed through LDS in wave order
-// (deterministic) and wave 0 runs the ordinary tile epilogue.  For K >= 128 (below that the waves would idle).
-// AN EXPERIMENT, off by default (spg_tune key 12 = 1 enables it): see launch_gemm_shape.
-template <bool WRED, int AMODE>
-__device__ __forceinline__ void spg_fewrow_sk_body(const SpgGemmParams& p, const int bx, const int by) {
-  extern __shared__ f32x4 smem[];
-  float* red = reinterpret_cast<float*>(smem);        // [3][16][64] partial accumulators of waves 1..3
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 31, h = lane >> 5;
-  if (p.stat_slots != nullptr && bx == 0 && by == 0 && threadIdx.x == 0)
-    spg_slots_count_add(p.stat_slots, WRED ? p.n_mask : p.N, p.stat_rows != 0 ? p.stat_rows : (long)p.M);
-  if constexpr (!WRED) {
-    if (p.fold.slots != nullptr) spg_bn_fold_fwd(p.fold, bx == 0 && by == 0);
-  } else {
-    if (p.fold_bwd.slots != nullptr) spg_bn_fold_bwd(p.fold_bwd, false);
-  }
-  const long m0 = (long)bx * 32;
-  const int mvalid = (int)min(32L, (long)p.M - m0);
-  const int n0 = by * 32;
-  const bool rowok = r < mvalid;
-  const long row = m0 + (rowok ? r : 0);
-  const int col = n0 + r;
-  const bool colok = col < p.N;
-  const int colc = colok ? col : 0;
-  const int K = p.K, nchunk = (K + SPG_KC - 1) / SPG_KC;
-  f32x16 acc;
-#pragma unroll
-  for (int q = 0; q < 16; ++q) acc[q] = 0.f;
-  for (int c = wave; c < nchunk; c += 4) {
-    const int k0 = c * SPG_KC + 16 * h;
-    f32x4 a[4], b[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int k = k0 + 4 * q;
-      const bool kin = k < K;                      // (a quad is addressable up to the next multiple of 4 of K: padded leading dimensions)
-      const int kc = kin ? k : 0;
-      const SpgQuad qc = spg_quad_consts<AMODE>(p.a, kc, K);
-      SpgRaw raw;
-      spg_load_raw1<AMODE>(p.a, row, kc, qc.nvalid, raw);
-      a[q] = spg_finish_raw<AMODE>(qc, raw, rowok && kin);
-      if constexpr (!WRED) {                       // weights [N, K]: this lane's output column, four consecutive reduction indices
-        const f32x4 w = *reinterpret_cast<const f32x4*>(p.W + (long)colc * p.ldw + kc);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) b[q][e] = (kin && k + e < K) ? w[e] : 0.f;
-      } else {                                     // weights [K, N] untransposed: one element per reduction index
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const bool ok = k + e < K;
-          const float w = p.W[(long)(ok ? k + e : 0) * p.ldw + colc];
-          b[q][e] = ok ? w : 0.f;
-        }
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q][e], b[q][e], acc, 0, 0, 0);
-  }
-  // ---- the four waves' partial sums, in wave order ----
-  if (wave != 0) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q) red[((wave - 1) * 16 + q) * 64 + lane] = acc[q];
-  }
-  __syncthreads();
-  if (wave != 0) return;
-#pragma unroll
-  for (int w = 0; w < 3; ++w)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc[q] += red[(w * 16 + q) * 64 + lane];
-  f32x16 accs[1][1];
-  accs[0][0] = acc;
-  SpgStatAcc<1> none;
-  none.has_sg = false;
-  spg_tile_epilogue<32, 32, 1, 1, WRED, false, false>(p, accs, red, bx, m0, mvalid, n0, none, false);
-}
-
-template <bool WRED, int AMODE>
-__global__ __launch_bounds__(SPG_THREADS) void spg_fewrow_sk_kernel(const SpgGemmParams p) {
-  spg_fewrow_sk_body<WRED, AMODE>(p, (int)blockIdx.x, (int)blockIdx.y);
-}
-#define SPG_SK_MIN_K 128
-#define SPG_SK_LDS (3 * 16 * 64 * sizeof(float))
-
 // ---- weights for the bf16 MFMA modes: split (hi = bf16(w), lo = bf16(w - hi)) and, for the data gradient, transposed ----
 __global__ __launch_bounds__(256) void spg_split_weights_kernel(const SpgSplitBatch b) {
   const SpgSplitJob j = b.jobs[blockIdx.y];
@@ -1370,7 +1276,7 @@ static int launch_gemm_t(const SpgGemmParams& p, hipStream_t stream, int* stat_p
   // last row tile): forward tiles that ARE complete leave through the vector store (dwordx4 row segments staged through LDS)
   // instead of 16 dword stores per accumulator block -- the epilogue decides per tile (spg_tile_epilogue)
   SpgGemmParams pv = p;
-  pv.vec_store = !WRED && p.Y != nullptr && (p.ldy & 3) == 0 && (((uintptr_t)p.Y) & 15) == 0 && !spg_tune_get(SPG_TUNE_NO_VEC_GENERIC);
+  pv.vec_store = !WRED && p.Y != nullptr && (p.ldy & 3) == 0 && (((uintptr_t)p.Y) & 15) == 0;
   if constexpr (IT == 32 && spg_gemm_variant(WRED, AMODE, false) >= 0) {
     if (grouped && spg_group_add(SPG_JOB_GEMM, spg_gemm_variant(WRED, AMODE, false), &pv, sizeof(pv), grid, lds, flops, stream, 2 + 2 * spg_cdiv(p.K, SPG_KC),
                                  [pv, grid, lds, stream]() -> int {
@@ -1384,37 +1290,10 @@ static int launch_gemm_t(const SpgGemmParams& p, hipStream_t stream, int* stat_p
   return 0;
 }
 
-// few rows, long reduction: the split-K form (spg_fewrow_sk_body) -- stand-alone or as a job of the open group
-template <bool WRED, int AMODE>
-static int launch_fewrow_sk(const SpgGemmParams& p, hipStream_t stream, int* stat_parts) {
-  const dim3 grid(spg_gemm_ntiles(p), spg_cdiv(p.N, 32));
-  if (stat_parts != nullptr) *stat_parts = (int)grid.x;
-  const double flops = 2.0 * (double)p.M * (double)p.N * (double)p.K;
-  const bool grouped = spg_group_accepts(stream);
-  ProfScope prof(stream, flops, SPG_PROF_TAG(1, 32, 32, WRED ? 1 : 0, AMODE, 0), !grouped);
-  prof.r.M = p.M; prof.r.N = p.N; prof.r.K = p.K;
-  auto direct = [p, grid, stream]() -> int {
-    hipLaunchKernelGGL((spg_fewrow_sk_kernel<WRED, AMODE>), grid, dim3(SPG_THREADS), SPG_SK_LDS, stream, p);
-    SPG_LAUNCH_CHECK();
-    return 0;
-  };
-  if (grouped && spg_group_add(SPG_JOB_GEMM, spg_gemm_sk_variant(WRED, AMODE), &p, sizeof(p), grid, SPG_SK_LDS, flops, stream,
-                               2 + 2 * spg_cdiv(spg_cdiv(p.K, SPG_KC), 4), direct))
-    return 0;
-  return direct();
-}
-
 template <bool WRED, int AMODE>
 static int launch_gemm_shape(const SpgGemmParams& p, hipStream_t stream, int* sp) {
-  if constexpr (AMODE == SPG_PRO_IDENT || (!WRED && AMODE == SPG_PRO_AFFINE) || (WRED && AMODE == SPG_PRO_BNBWD)) {
-    // OPT-IN (spg_tune key 12): measured no faster than the 32 x 128 kernel on the step (1.404 vs 1.401 ms, same box,
-    // profiles/r04_splitk_experiment.txt) -- a link of an FC chain is dispatch + statistics fold + first loads + epilogue; the
-    // chunk loop this form shortens is the smaller part, and without operand prefetch its chunks pay the memory latency each
-    // (round 5: also tried as the default for the one long reduction of the step, the data gradient of the filter network's last
-    // layer, K = 1024 -- 1.1949 vs 1.1947 ms: the group it rides in is not bounded by it)
-    if (spg_tune_get(SPG_TUNE_SPLITK) && p.rows_per_tile == SPG_FC_ROWS && p.K >= SPG_SK_MIN_K && p.pool_out == nullptr)
-      return launch_fewrow_sk<WRED, AMODE>(p, stream, sp);
-  }
+  // A split-K form of the few-row launches (the waves of a 32 x 32 tile split the reduction chunks) was tried and gave nothing,
+  // on the step or for the K = 1024 data gradient alone; its code is gone (profiles/r04_splitk_experiment.txt).
   if (p.rows_per_tile <= 32) return launch_gemm_t<32, 128, 1, 4, WRED, AMODE>(p, stream, sp);   // few rows (FC layers, filter net)
   if (p.N <= 32) return launch_gemm_t<128, 32, 4, 1, WRED, AMODE>(p, stream, sp);
   if (p.N <= 64) return launch_gemm_t<128, 64, 2, 2, WRED, AMODE>(p, stream, sp);
@@ -1759,31 +1638,20 @@ size_t spg_wgrad_workspace_floats(long M, int N, int K) {
   return w > c ? w : c;
 }
 
-// Slices and probes (spg_gemm.h: spg_queue_wgrad_leaf): while g_wgrad_slice_n > 0 the launch functions below issue ONLY the
-// splits [g_wgrad_slice0, g_wgrad_slice0 + g_wgrad_slice_n) of the weight gradient, as a job of the open group (never as a
-// kernel of its own: the stand-alone kernels have no split offset); while g_wgrad_probe is set nothing is launched and the id
-// of the grouped body the launch WOULD use is left in g_wgrad_probe_variant (-1: none -- the launch cannot be sliced).
-namespace { thread_local int g_wgrad_slice0 = 0, g_wgrad_slice_n = 0, g_wgrad_probe_variant = -1; thread_local bool g_wgrad_probe = false; }
-
 template <int IT, int JT, int WI, int WJ, int AMODE, int BMODE>
 static int launch_wgrad_t(const SpgWgradParams& p, int nsplit, hipStream_t stream) {
   const size_t lds = (size_t)((AMODE >= 0 && BMODE >= 0) ? 2 : 1) * SPG_KC * (IT + 4 + JT + 4) * sizeof(float);
-  const bool sliced = g_wgrad_slice_n > 0;
-  dim3 grid(sliced ? g_wgrad_slice_n : nsplit, spg_cdiv(p.N, IT), spg_cdiv(p.K, JT));
-  const double flops = 2.0 * (double)p.M * (double)p.N * (double)p.K * (sliced ? (double)g_wgrad_slice_n / nsplit : 1.0);
+  dim3 grid(nsplit, spg_cdiv(p.N, IT), spg_cdiv(p.K, JT));
+  const double flops = 2.0 * (double)p.M * (double)p.N * (double)p.K;
   // reductions over few rows (FC layers, filter net, recurrent cell) inside an open group become jobs of its one launch; the
-  // wide convolutions' weight gradients (performance-critical, own occupancy bounds) never do -- except as slices (above)
-  const bool grouped = (sliced || p.M <= SPG_GROUP_MAX_WGRAD_ROWS) && spg_group_accepts(stream);
-  ProfScope prof(stream, flops, 0, !grouped && !g_wgrad_probe);
-  // -> 1: taken (by the group, or recorded by a probe), 0: launch it directly, < 0: error
-  auto try_group = [&](int variant) -> int {
-    if (g_wgrad_probe) { g_wgrad_probe_variant = variant; return 1; }
-    if (grouped && variant >= 0 && spg_group_add(SPG_JOB_WGRAD, variant, &p, sizeof(p), grid, lds, flops, stream, 2 + 2 * (p.rows_per_split / SPG_KC),
-                                                 nullptr, sliced ? g_wgrad_slice0 : 0)) return 1;
-    if (sliced) { spg_set_error("a weight-gradient slice needs an open group and a grouped body (variant %d)", variant); return -1; }
-    return 0;
+  // wide convolutions' weight gradients (performance-critical, own occupancy bounds) never do
+  const bool grouped = p.M <= SPG_GROUP_MAX_WGRAD_ROWS && spg_group_accepts(stream);
+  ProfScope prof(stream, flops, 0, !grouped);
+  // true: taken by the group
+  auto try_group = [&](int variant) -> bool {
+    return grouped && variant >= 0 && spg_group_add(SPG_JOB_WGRAD, variant, &p, sizeof(p), grid, lds, flops, stream, 2 + 2 * (p.rows_per_split / SPG_KC));
   };
-#define SPG_TRY_GROUP(v) { const int tg_ = try_group(v); if (tg_ != 0) return tg_ < 0 ? 1 : 0; }
+#define SPG_TRY_GROUP(v) { if (try_group(v)) return 0; }
   if constexpr (AMODE >= 0 && BMODE >= 0 && AMODE != SPG_PRO_CLOUD && BMODE != SPG_PRO_CLOUD) {
     auto mode_ok = [](int mode, const SpgOperand& d, int nch) {
       if (mode == SPG_PRO_AFFINE) return d.c0 != nullptr && d.n_affine >= nch;
@@ -1807,8 +1675,6 @@ static int launch_wgrad_t(const SpgWgradParams& p, int nsplit, hipStream_t strea
         }
       }
       if (prec == 0) SPG_TRY_GROUP(spg_wgrad_variant(IT, JT, AMODE, BMODE, true, false))
-      else if (g_wgrad_probe) { g_wgrad_probe_variant = -1; return 0; }
-      else if (sliced) { spg_set_error("weight-gradient slices are fp32-MFMA launches"); return 1; }
       if (prec == 3) hipLaunchKernelGGL((spg_wgrad_kernel<IT, JT, WI, WJ, AMODE, BMODE, true, 3>), grid, dim3(SPG_THREADS), lds, stream, p);
       else if (prec == 1) hipLaunchKernelGGL((spg_wgrad_kernel<IT, JT, WI, WJ, AMODE, BMODE, true, 1>), grid, dim3(SPG_THREADS), lds, stream, p);
       else
@@ -2006,8 +1872,8 @@ int spg_flush_deferred_reduce(hipStream_t stream) {
 }
 
 // (`used` only ever grows during a queue's life: a flush in the middle of a pass -- job table full -- sums and forgets the JOBS
-//  queued so far but never hands out their arena space again, so partial buffers captured by pending leaves (spg_queue_wgrad_leaf)
-//  stay theirs until the queue dies; a pass that needs more than the arena fails with an argument error instead of wrapping around)
+//  queued so far but never hands out their arena space again, so a partial buffer stays its owner's until the queue dies; a pass
+//  that needs more than the arena fails with an argument error instead of wrapping around)
 static int queue_take(SpgReduceQueue& q, size_t floats, float** out, hipStream_t stream) {
   if (q.njobs == SPG_MAX_REDUCE_JOBS) SPG_TRY(spg_flush_reduce(q, stream));
   SPG_CHECK_ARG(q.arena != nullptr && q.used + floats <= q.arena_floats, "reduction arena too small");
@@ -3187,7 +3053,7 @@ __device__ __forceinline__ void spg_multi_body() {
   j = __builtin_amdgcn_readfirstlane(j);
   const SpgJobHdr h = a.hdr[j];
   const int b = (int)blockIdx.x - a.first_block[j];
-  const int bx = b % h.gx + h.bx0, by = (b / h.gx) % h.gy, bz = b / (h.gx * h.gy);
+  const int bx = b % h.gx, by = (b / h.gx) % h.gy, bz = b / (h.gx * h.gy);
   const unsigned char* P = a.arena + h.offset;
 #define SPG_P(T) (*reinterpret_cast<const T*>(P))
   if (h.kind == SPG_JOB_GEMM) {
@@ -3203,10 +3069,6 @@ __device__ __forceinline__ void spg_multi_body() {
       case 7: spg_rowgemm_body<32, 128, 1, 4, true, SPG_PRO_BNBWD, false>(SPG_P(SpgGemmParams), bx, by); break;
       case 8: if constexpr (HEAVY) spg_rowgemm_body<32, 128, 1, 4, true, SPG_PRO_BNBWD, true>(SPG_P(SpgGemmParams), bx, by); break;
       case 9: spg_rowgemm_body<32, 128, 1, 4, true, -1, false>(SPG_P(SpgGemmParams), bx, by); break;
-      case 10: spg_fewrow_sk_body<false, SPG_PRO_IDENT>(SPG_P(SpgGemmParams), bx, by); break;
-      case 11: spg_fewrow_sk_body<false, SPG_PRO_AFFINE>(SPG_P(SpgGemmParams), bx, by); break;
-      case 12: spg_fewrow_sk_body<true, SPG_PRO_IDENT>(SPG_P(SpgGemmParams), bx, by); break;
-      case 13: spg_fewrow_sk_body<true, SPG_PRO_BNBWD>(SPG_P(SpgGemmParams), bx, by); break;
       default: break;
     }
   } else if (h.kind == SPG_JOB_WGRAD) {
@@ -3348,13 +3210,13 @@ SpgGroupBypass::SpgGroupBypass(bool on) : on_(on) { if (on_) ++g_bypass; }
 SpgGroupBypass::~SpgGroupBypass() { if (on_) --g_bypass; }
 static bool spg_group_accepts(hipStream_t stream) { return g_grp.open && g_grp.st == stream && g_grp.rc == 0 && g_bypass == 0; }
 
-// Jobs that RIDE in somebody else's group (rider stages, riding reductions, leaves) while > 0: the group's own jobs -- the ones the
+// Jobs that RIDE in somebody else's group (rider stages, riding reductions) while > 0: the group's own jobs -- the ones the
 // next launch of the stream waits for -- get the first workgroup slots of the launch (round 5: measured with the job spans of an
 // attribution build, bench.py --group-trace: the head's data gradient started 17 us into a 42 us launch, behind 581 workgroups of
 // riding weight gradients)
 // weight: relative duration of ONE workgroup of the job (sequential reduction chunks); decides the launch order
 static bool spg_group_add(int kind, int variant, const void* params, size_t bytes, dim3 grid, size_t lds, double flops, hipStream_t stream, int weight,
-                          std::function<int()> direct, int bx0) {
+                          std::function<int()> direct) {
   SpgGroupState& g = g_grp;
   const size_t need = (bytes + 15) & ~(size_t)15;
   if (!spg_group_accepts(stream) || variant < 0 || need > SPG_GROUP_ARENA_BYTES) return false;
@@ -3366,7 +3228,7 @@ static bool spg_group_add(int kind, int variant, const void* params, size_t byte
   }
   SpgJobHdr& h = g.a.hdr[g.a.njobs];
   h.kind = kind; h.variant = variant; h.gx = (int)grid.x; h.gy = (int)grid.y; h.gz = (int)grid.z;
-  h.offset = (int)g.used; h.weight = weight + ((g_riding > 0 || g_tune[SPG_TUNE_NO_OWNER_FIRST]) ? 0 : SPG_OWNER_WEIGHT); h.bx0 = bx0;
+  h.offset = (int)g.used; h.weight = weight + (g_riding > 0 ? 0 : SPG_OWNER_WEIGHT); h.reserved = 0;
   g.direct = g.a.njobs == 0 ? std::move(direct) : nullptr;
   memcpy(g.a.arena + g.used, params, bytes);
   g.used += need;
@@ -3430,85 +3292,6 @@ int spg_riders_drain(hipStream_t stream) {
     SPG_TRY(grp.flush());               // flush() pulls exactly one stage
   }
   return 0;
-}
-
-// ---- leaves (spg_gemm.h) ----
-namespace {
-struct SpgLeaf { SpgStage issue; double cost; };
-thread_local std::vector<SpgLeaf> g_leaves;
-thread_local size_t g_leaf_next = 0;
-}  // namespace
-void spg_leaf_push(SpgStage issue, double cost) { g_leaves.push_back(SpgLeaf{std::move(issue), cost}); }
-int spg_leaf_pending() { return (int)(g_leaves.size() - g_leaf_next); }
-void spg_leaf_clear() { g_leaves.clear(); g_leaf_next = 0; }
-int spg_leaf_ride(hipStream_t stream, int launches_left) {
-  if (spg_leaf_pending() == 0 || !spg_group_accepts(stream)) return 0;
-  double total = 0.0;
-  for (size_t i = g_leaf_next; i < g_leaves.size(); ++i) total += g_leaves[i].cost;
-  const double share = total / (launches_left > 1 ? launches_left : 1);
-  double taken = 0.0;
-  SpgRidingScope riding;
-  while (g_leaf_next < g_leaves.size() && (taken == 0.0 || taken + 0.5 * g_leaves[g_leaf_next].cost <= share)) {
-    SpgLeaf leaf = std::move(g_leaves[g_leaf_next++]);
-    taken += leaf.cost;
-    SPG_TRY(leaf.issue(stream));
-  }
-  if (g_leaf_next >= g_leaves.size()) spg_leaf_clear();
-  return 0;
-}
-int spg_leaf_drain(hipStream_t stream) {
-  while (spg_leaf_pending() > 0) {
-    SpgGroupScope grp(stream);      // (a scope of its own when none is open; inside an open one the leaves join it)
-    while (spg_leaf_pending() > 0) {
-      SpgLeaf leaf = std::move(g_leaves[g_leaf_next++]);
-      SPG_TRY(leaf.issue(stream));
-    }
-    if (grp.active()) SPG_TRY(grp.flush());
-  }
-  spg_leaf_clear();
-  return 0;
-}
-
-// the weight gradient `p` -> dW as `nslice` leaves (splits of its plan in contiguous ranges); the LAST leaf queues the summation
-// of the partials in `q`, which must therefore outlive the leaves (spg_leaf_drain before its flush).  false: this launch has no
-// grouped body / a single split / no room -- the caller issues it the ordinary way.
-bool spg_queue_wgrad_leaf(SpgReduceQueue& q, SpgWgradParams p, float* dW, int nslice, hipStream_t stream) {
-  if (p.M <= 0 || p.N <= 0 || p.K <= 0 || nslice < 1 || g_tune[SPG_TUNE_NO_GROUP] || !g_tune[SPG_TUNE_LEAVES]) return false;
-  int it, jt, ns, rps;
-  wgrad_plan(p.M, p.N, p.K, &it, &jt, &ns, &rps);
-  if (ns < 2) return false;
-  p.colsum = nullptr;
-  g_wgrad_probe = true; g_wgrad_probe_variant = -1;
-  const int prc = spg_launch_wgrad_partials(p, dW, stream);
-  g_wgrad_probe = false;
-  if (prc != 0 || g_wgrad_probe_variant < 0) return false;
-  if (q.njobs + 1 > SPG_MAX_REDUCE_JOBS || q.arena == nullptr || q.used + (size_t)ns * p.N * p.K > q.arena_floats) return false;
-  float* part = nullptr;
-  if (queue_take(q, (size_t)ns * p.N * p.K, &part, stream) != 0) return false;
-  if (nslice > ns) nslice = ns;
-  SpgReduceQueue* qp = &q;
-  const double cost = 2.0 * (double)p.M * p.N * p.K / nslice;
-  for (int sidx = 0; sidx < nslice; ++sidx) {
-    const int s0 = (int)((long)ns * sidx / nslice), s1 = (int)((long)ns * (sidx + 1) / nslice);
-    const bool last = sidx + 1 == nslice;
-    spg_leaf_push([p, part, dW, s0, s1, ns, last, qp](hipStream_t st) -> int {
-      int rc = 0;
-      {
-        SpgGroupScope own(st);      // no-op inside the caller's open scope; a launch of its own otherwise (drain without a scope)
-        g_wgrad_slice0 = s0; g_wgrad_slice_n = s1 - s0;
-        rc = spg_launch_wgrad_partials(p, part, st);
-        g_wgrad_slice0 = 0; g_wgrad_slice_n = 0;
-        if (rc == 0 && own.active()) rc = own.flush();
-      }
-      if (rc == 0 && last) {
-        if (qp->njobs == SPG_MAX_REDUCE_JOBS) { spg_set_error("reduction queue full behind a weight-gradient leaf"); return 1; }
-        SpgReduceJob& j = qp->jobs[qp->njobs++];
-        j.partial = part; j.out = dW; j.nsplit = ns; j.n = p.N * p.K;
-      }
-      return rc;
-    }, cost);
-  }
-  return true;
 }
 
 int SpgGroupScope::flush() {

@@ -36,6 +36,10 @@ def test_size_queries(hip):
     c2 = ops.make_eccrnn_cfg(32, 10, True, True, True, True, [13, 32, 128, 64, 1024], 2, False)
     assert hip.spg_eccrnn_workspace_bytes(ctypes.byref(c2), 1000, 5000, 1) > 0
     assert hip.spg_graph_workspace_bytes(1000, 1000, 5000) >= 4 * (2 * 1001 + 3 * 5000)
+    # retired spg_tune keys (their code paths are gone): switching one on fails loudly, 0 stays accepted
+    for k in (9, 12, 13, 16, 19):
+        assert hip.spg_tune(k, 1) == -1, k
+        assert hip.spg_tune(k, 0) >= 0, k
 
 
 def test_graphconvinfo_bit_exact_and_collate():

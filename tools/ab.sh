@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of spg_tune switches on ONE box, interleaved:  tools/ab.sh "<tuneA>" "<tuneB>" [reps]   (e.g. tools/ab.sh "" "9:1" 3)
+# A/B of spg_tune switches on ONE box, interleaved:  tools/ab.sh "<tuneA>" "<tuneB>" [reps]   (e.g. tools/ab.sh "" "14:1" 3)
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 A="$1"; B="$2"; N=${3:-3}
 for i in $(seq $N); do
