@@ -334,6 +334,24 @@ int spg_prune_reduce(const float* xyz, const uint8_t* rgb, const uint8_t* labels
                      int n_labels, int n_objects, float* out_xyz, uint8_t* out_rgb, uint32_t* out_labels, uint32_t* out_objects,
                      int32_t* error_flag, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Exact k-nearest neighbours (partition/graphs.py:11-73 compute_graph_nn / compute_graph_nn_2, partition/provider.py:681-687
+ * interpolate_labels; sklearn NearestNeighbors(algorithm='kd_tree') in the reference) over a uniform grid of the reference set.
+ * Order: float64 squared distance ((dx*dx + dy*dy) + dz*dz, dx = (double)q.x - (double)p.x, no fused multiply-add), ties by
+ * point index; in self-query mode the query point itself is dropped.  Results are in query order and do not depend on the
+ * cell size.  spg_knn_build indexes ref_xyz float32 [n_ref, 3] into the workspace (cell_size 0 = automatic, ~32 points per
+ * occupied cell; > 0 = that cell, for tuning and tests).  spg_knn_query on the SAME workspace: self_query = 1 searches the
+ * reference points themselves (query_xyz ignored, n_query == n_ref > k), else query_xyz float32 [n_query, 3] (k <= n_ref),
+ * processed in internal chunks sized by the workspace.  idx_out int32 [n_query, k]; dist_out float32 [n_query, k] =
+ * (float)sqrt(d2), or NULL.  1 <= k <= 47 (k + 1 <= 48).  error_flag (device int32, may be NULL): 1 = a non-finite coordinate (the outputs
+ * are then undefined; a non-finite reference point spoils the index, a non-finite query only that call).  Workspace: spg_knn_workspace_bytes(n_ref, largest n_query passed, k) (n_query 0 for self queries). */
+size_t spg_knn_workspace_bytes(long n_ref, long n_query, int k);
+int spg_knn_build(const float* ref_xyz, long n_ref, float cell_size, int32_t* error_flag, void* workspace, size_t workspace_bytes,
+                  void* stream);
+int spg_knn_query(const float* query_xyz, long n_query, long n_ref, int k, int self_query, int32_t* idx_out, float* dist_out,
+                  int32_t* error_flag, void* workspace, size_t workspace_bytes, void* stream);
+/* queries per internal chunk spg_knn_query uses for n_query queries on this workspace (0: too small for any chunk) */
+long spg_knn_query_chunk(long n_ref, long n_query, size_t workspace_bytes);
+
 /* Random streams of the loader generated on the device (optional; the default keeps numpy's streams on the host so
  * that seeded runs reproduce the reference's clouds): Philox4x32-10 keyed by (seed, superpoint id, step).  counts /
  * ids int64 [S], slot int32 [S] (row of the cloud tensor or -1) -> sample_idx int32 [S, npts] (spg.py:207-214), M

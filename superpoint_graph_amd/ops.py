@@ -836,3 +836,81 @@ def prune(xyz, voxel_size: float, rgb=None, labels=None, objects=None, n_labels:
     if int(err.item()) & 2:
         raise IndexError('prune: a label / object id exceeds n_labels / n_objects')
     return out_xyz, out_rgb, out_lab, out_obj
+
+
+KNN_MAX_K = 47          # k + 1 <= 48: the largest top-k list the query kernels keep in registers without scratch
+
+
+class KnnIndex:
+    """Exact k-nearest-neighbour index of a device point set (csrc/spg_knn.hip): ref_xyz f32 [n,3] on the GPU, indexed once
+    into a uniform grid; query() / self_query() answer on the device.  Order: float64 squared distance (dx*dx + dy*dy) + dz*dz
+    (no fused multiply-add), ties by point index; self queries drop the query point itself.  The results do not depend on
+    cell_size (None = automatic, ~32 points per occupied cell; a value is for tuning and tests).  query_capacity: the largest
+    query set the workspace is sized for in one internal chunk (larger sets are streamed in chunks)."""
+
+    def __init__(self, ref_xyz, cell_size=None, query_capacity: int = 0):
+        _req(ref_xyz, torch.float32, 'ref_xyz')
+        if ref_xyz.dim() != 2 or ref_xyz.shape[1] != 3:
+            raise ValueError(f'knn: ref_xyz must be [n, 3], got {tuple(ref_xyz.shape)}')
+        n = int(ref_xyz.shape[0])
+        if n == 0:
+            raise ValueError('knn: empty reference set')
+        if n >= 2 ** 32 - 1:
+            raise ValueError('knn: point indices are uint32: at most 2^32 - 2 reference points')
+        if cell_size is not None and not (float(cell_size) > 0.0):
+            raise ValueError(f'knn: cell_size must be > 0, got {cell_size}')
+        L, dev = lib(), ref_xyz.device
+        self.ref, self.n = ref_xyz, n
+        self.ws = _u8_workspace(L.spg_knn_workspace_bytes(n, int(query_capacity), 1), dev)
+        self.err = torch.zeros(1, dtype=torch.int32, device=dev)
+        check(L.spg_knn_build(_ptr(ref_xyz), n, float(cell_size or 0.0), _ptr(self.err), _ptr(self.ws), self.ws.numel(), _stream()),
+              'spg_knn_build')
+
+    def _k(self, k, n_avail):
+        k = int(k)
+        if k < 1:
+            raise ValueError(f'knn: k must be >= 1, got {k}')
+        if k + 1 > KNN_MAX_K + 1:
+            raise ValueError(f'knn: k + 1 = {k + 1} exceeds the limit of {KNN_MAX_K + 1} (k <= {KNN_MAX_K})')
+        if k > n_avail:
+            raise ValueError(f'knn: Expected n_neighbors <= n_samples, but n_samples = {self.n}, n_neighbors = '
+                             f'{k + 1 if n_avail < self.n else k}')
+        return k
+
+    def _run(self, q, nq, k, self_query, distances):
+        dev = self.ref.device
+        idx = torch.empty(nq, k, dtype=torch.int32, device=dev)
+        dist = torch.empty(nq, k, dtype=torch.float32, device=dev) if distances else None
+        check(lib().spg_knn_query(_ptr(q), nq, self.n, k, int(self_query), _ptr(idx), _ptr(dist), _ptr(self.err), _ptr(self.ws),
+                                  self.ws.numel(), _stream()), 'spg_knn_query')
+        if int(self.err.item()) & 1:
+            raise ValueError('knn: the input contains NaN or infinity')
+        return idx, dist
+
+    def query_chunk(self, n_query: int) -> int:
+        """queries per internal chunk that query() uses for n_query queries on this index's workspace."""
+        return int(lib().spg_knn_query_chunk(self.n, int(n_query), self.ws.numel()))
+
+    def self_query(self, k, distances=True):
+        """k nearest other points of every reference point -> (idx i32 [n, k], dist f32 [n, k] or None)."""
+        return self._run(None, self.n, self._k(k, self.n - 1), True, distances)
+
+    def query(self, query_xyz, k, distances=True):
+        """k nearest reference points of every query point -> (idx i32 [m, k], dist f32 [m, k] or None)."""
+        _req(query_xyz, torch.float32, 'query_xyz')
+        if query_xyz.dim() != 2 or query_xyz.shape[1] != 3:
+            raise ValueError(f'knn: query_xyz must be [m, 3], got {tuple(query_xyz.shape)}')
+        nq = int(query_xyz.shape[0])
+        if nq >= 2 ** 32 - 1:
+            raise ValueError('knn: at most 2^32 - 2 query points per call')
+        return self._run(query_xyz, nq, self._k(k, self.n), False, distances)
+
+
+def knn(ref_xyz, k: int, query_xyz=None, cell_size=None, distances: bool = True):
+    """Exact k nearest neighbours on the device (sklearn NearestNeighbors(algorithm='kd_tree') in the reference's
+    partition/graphs.py:11-73 and provider.py:681-687).  ref_xyz f32 [n,3]; query_xyz f32 [m,3] or None = self query (the point
+    itself is dropped) -> (idx int32 [m, k], distances float32 [m, k] or None), in query order.  1 <= k <= KNN_MAX_K."""
+    index = KnnIndex(ref_xyz, cell_size, 0 if query_xyz is None else int(query_xyz.shape[0]))
+    if query_xyz is None:
+        return index.self_query(k, distances)
+    return index.query(query_xyz, k, distances)

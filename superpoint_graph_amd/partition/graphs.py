@@ -1,5 +1,7 @@
-"""`compute_sp_graph` / `compute_geof` with the reference's signatures (partition/graphs.py:75, partition/ply_c/ply_c.cpp:384 as
-bound by `libply_c.compute_geof(xyz, target, k_nn)`), computed by the HIP library (csrc/spg_spgraph.hip).
+"""`compute_graph_nn` / `compute_graph_nn_2` / `compute_sp_graph` / `compute_geof` with the reference's signatures
+(partition/graphs.py:11-75, partition/ply_c/ply_c.cpp:384 as bound by `libply_c.compute_geof(xyz, target, k_nn)`), computed by
+the HIP library (csrc/spg_knn.hip: exact kNN over a uniform grid; csrc/spg_spgraph.hip).  The kNN graphs order neighbours by
+float64 squared distance and then by index (sklearn leaves the order of equidistant points open) and never contain self loops.
 
 What stays on the host: scipy's Delaunay triangulation (qhull; a different algorithm class) -- everything
 after it (12 T candidate pairs -> unique interface edges -> d_max filter -> ordering by component pair -> per-superpoint and
@@ -103,3 +105,44 @@ def prune(xyz, voxel_size, rgb, labels, objects, n_labels, n_objects):
     obj_d = up(np.ascontiguousarray(objects, dtype=np.uint32).reshape(n).view(np.int32)) if (n_labels > 0 and n_objects > 0) else None
     x, c, l, o = ops.prune(up(xyz), float(np.float32(voxel_size)), rgb_d, lab_d, obj_d, int(n_labels), int(n_objects))
     return x.cpu().numpy(), c.cpu().numpy(), l.cpu().numpy().view(np.uint32), o.cpu().numpy().view(np.uint32)
+
+
+def _knn_self(xyz, k):
+    xyz = np.ascontiguousarray(xyz, dtype=np.float32)
+    if xyz.ndim != 2 or xyz.shape[1] != 3:
+        raise ValueError(f'knn graph: xyz [n, 3] expected, got {xyz.shape}')
+    if not np.all(np.isfinite(xyz)):
+        raise ValueError('Input contains NaN or infinity.')
+    n = len(xyz)
+    if n <= k:
+        raise ValueError(f'Expected n_neighbors <= n_samples, but n_samples = {n}, n_neighbors = {k + 1}')
+    idx, dist = ops.knn(ops.upload(torch.from_numpy(xyz), _dev()), int(k))
+    return n, idx.cpu().numpy().view(np.uint32), dist.cpu().numpy()
+
+
+def compute_graph_nn(xyz, k_nn):
+    """compute the knn graph (reference partition/graphs.py:11-24): {'is_nn': True, 'source', 'target' uint32 [n * k_nn],
+    'distances' float32 [n * k_nn]}, each point's k_nn nearest other points in (distance, index) order."""
+    n, nb, dist = _knn_self(xyz, int(k_nn))
+    graph = dict([("is_nn", True)])
+    graph["source"] = np.repeat(np.arange(n, dtype=np.uint32), int(k_nn))
+    graph["target"] = nb.reshape(-1).copy()
+    graph["distances"] = dist.reshape(-1).copy()
+    return graph
+
+
+def compute_graph_nn_2(xyz, k_nn1, k_nn2, voronoi=0.0):
+    """compute simultaneously 2 knn structures (reference partition/graphs.py:26-73): one search with k_nn2 neighbours; the
+    graph dictionary holds the first k_nn1 columns, target2 (uint32 [n * k_nn2]) all of them.  voronoi > 0 (the Delaunay
+    adjacency, qhull) is not supported."""
+    assert k_nn1 <= k_nn2, "knn1 must be smaller than knn2"
+    if voronoi > 0:
+        raise NotImplementedError('compute_graph_nn_2: voronoi > 0 (Delaunay adjacency) is not supported on the device')
+    k1, k2 = int(k_nn1), int(k_nn2)
+    n, nb, dist = _knn_self(xyz, k2)
+    target2 = nb.reshape(-1).copy()
+    graph = dict([("is_nn", True)])
+    graph["source"] = np.repeat(np.arange(n, dtype=np.uint32), k1)
+    graph["target"] = np.ascontiguousarray(nb[:, :k1]).reshape(-1)
+    graph["distances"] = np.ascontiguousarray(dist[:, :k1]).reshape(-1)
+    return graph, target2
