@@ -352,6 +352,42 @@ int spg_knn_query(const float* query_xyz, long n_query, long n_ref, int k, int s
 /* queries per internal chunk spg_knn_query uses for n_query queries on this workspace (0: too small for any chunk) */
 long spg_knn_query_chunk(long n_ref, long n_query, size_t workspace_bytes);
 
+/* Graph contrastive loss of the learned partition and its cross-partition weights (supervized_partition/losses.py:24-64 and
+ * :130-166, libply_c.connected_comp with cutoff 0); csrc/spg_edgeloss.hip.  n vertices, E edges: 1 <= n < 2^31 - 1, 0 <= E < 2^30.
+ * spg_edgegraph_build: src / tgt int64 [E] -> rowptr int32 [n + 1], inc uint32 [2E] (edge << 1 | side, side 0 = the vertex is the
+ * edge's source, 1 = its target; the entries of a vertex in ascending edge id) and ends int32 [E, 2] (source, target).  Deterministic.
+ * error_flag (device int32): 1 = an index outside [0, n) (that end is left out of the CSR and reads vertex 0 in ends).
+ * spg_edge_forward: mode 1 = diff only, 2 = loss from a given diff, 3 = both in one launch (bit-identical to 1 then 2).
+ * emb float32 [n, d], d <= 64; dist_type 0 euclidian, 1 intrinsic, 2 scalar; intra 0 tv, 1 laplacian, 2 TVH; inter 0 zhang,
+ * 1 TVminus.  diff float32 [E]; dx float32 [E] = d diff / d dot (intrinsic only, else may be NULL); dl float32 [E] = d term / d diff;
+ * loss_out float64 [2] = loss1, loss2, summed in a fixed order.  Workspace (modes 2, 3): spg_edge_forward_workspace_bytes(E).
+ * spg_edge_loss_backward: grad_diff[e] = up[is_transition[e] != 0] * dl[e] (up float32 [2]: the gradients of loss1, loss2).
+ * spg_edge_backward: grad_emb[v] = sum over the incidences of v in CSR order of g_e * d diff_e / d emb_v, g_e = up[.] * dl[e]
+ * (dl != NULL) plus grad_diff[e] (grad_diff != NULL); float64 accumulation, no atomics, bit-identical from run to run.
+ * spg_connected_components: active uint8 [E] -> in_component int32 [n], component_size int32 [n] (the first *n_components
+ * entries), n_components device int32; numbered by ascending smallest member.  Synchronises the stream once per round (the host
+ * reads a "changed" word); returns -2 if the bounded number of rounds does not settle.
+ * spg_xpart_weights: pred_in_component int32 [n], is_transition uint8 [E] -> weights float32 [E] = 1 + min(size_a, size_b) /
+ * count(pair) * factor (float64, rounded once) on transition edges, 1 elsewhere; also returns the cross components. */
+size_t spg_edgegraph_workspace_bytes(long n, long E);
+int spg_edgegraph_build(const int64_t* src, const int64_t* tgt, long E, long n, int32_t* rowptr, uint32_t* inc, int32_t* ends,
+                        int32_t* error_flag, void* workspace, size_t workspace_bytes, void* stream);
+size_t spg_edge_forward_workspace_bytes(long E);
+int spg_edge_forward(int mode, const float* emb, long n, int d, const int32_t* ends, long E, int dist_type, int intra, int inter,
+                     const uint8_t* is_transition, const float* weights, float* diff, float* dx, float* dl, double* loss_out,
+                     void* workspace, size_t workspace_bytes, void* stream);
+int spg_edge_loss_backward(const float* dl, const uint8_t* is_transition, const float* up, long E, float* grad_diff, void* stream);
+int spg_edge_backward(const float* emb, long n, int d, const int32_t* rowptr, const uint32_t* inc, const int32_t* ends, long E,
+                      int dist_type, const float* dl, const uint8_t* is_transition, const float* up, const float* grad_diff,
+                      const float* dx, float* grad_emb, void* stream);
+size_t spg_cc_workspace_bytes(long n);
+int spg_connected_components(const int32_t* ends, const uint8_t* active, long E, long n, int32_t* in_component,
+                             int32_t* component_size, int32_t* n_components, void* workspace, size_t workspace_bytes, void* stream);
+size_t spg_xpart_workspace_bytes(long n, long E);
+int spg_xpart_weights(const int32_t* ends, long E, long n, const int32_t* pred_in_component, const uint8_t* is_transition,
+                      double factor, float* weights, int32_t* in_component, int32_t* component_size, int32_t* n_components,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* Random streams of the loader generated on the device (optional; the default keeps numpy's streams on the host so
  * that seeded runs reproduce the reference's clouds): Philox4x32-10 keyed by (seed, superpoint id, step).  counts /
  * ids int64 [S], slot int32 [S] (row of the cloud tensor or -1) -> sample_idx int32 [S, npts] (spg.py:207-214), M

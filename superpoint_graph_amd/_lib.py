@@ -138,6 +138,16 @@ SIGNATURES = {
     'spg_knn_build': (_i, [_p, _l, ctypes.c_float, _p, _p, _sz, _p]),
     'spg_knn_query': (_i, [_p, _l, _l, _i, _i, _p, _p, _p, _p, _sz, _p]),
     'spg_knn_query_chunk': (_l, [_l, _l, _sz]),
+    'spg_edgegraph_workspace_bytes': (_sz, [_l, _l]),
+    'spg_edgegraph_build': (_i, [_p, _p, _l, _l, _p, _p, _p, _p, _p, _sz, _p]),
+    'spg_edge_forward_workspace_bytes': (_sz, [_l]),
+    'spg_edge_forward': (_i, [_i, _p, _l, _i, _p, _l, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    'spg_edge_loss_backward': (_i, [_p, _p, _p, _l, _p, _p]),
+    'spg_edge_backward': (_i, [_p, _l, _i, _p, _p, _p, _l, _i, _p, _p, _p, _p, _p, _p, _p]),
+    'spg_cc_workspace_bytes': (_sz, [_l]),
+    'spg_connected_components': (_i, [_p, _p, _l, _l, _p, _p, _p, _p, _sz, _p]),
+    'spg_xpart_workspace_bytes': (_sz, [_l, _l]),
+    'spg_xpart_weights': (_i, [_p, _l, _l, _p, _p, ctypes.c_double, _p, _p, _p, _p, _p, _sz, _p]),
     'spg_edge_features': (_i, [ctypes.POINTER(EdgeFeatureSpecs), _p, _l, _p, _p, _p, _p]),
     'spg_loader_random': (_i, [_p, _p, _p, _i, _i, _i, ctypes.c_uint64, ctypes.c_uint32, _i, ctypes.c_float, _i, ctypes.c_float, _i, _p, _p, _p, _p]),
     'spg_cross_entropy_fwd': (_i, [_p, _p, _p, _i, _i, ctypes.c_int64, _i, _p, _p, _p, _p]),
