@@ -8,7 +8,7 @@
 //   spg_spg_tet_edges    one thread per (tetrahedron, vertex pair): both directions of every interface pair as a 64-bit key
 //                        (source << 32 | target), appended with one atomic per wavefront;
 //   spg_spg_unique_edges radix sort of the keys (rocPRIM), first-of-run + length flags -- the float32 distance is evaluated
-//                        in the reference's operation order (graphs.py:113, no fused multiply-add), so the SET of surviving edges
+//                        in the reference's operation order (graphs.py:113, no fused multiply-add: sumsq3_rn_f32 / sqrt_rn_f32), so the SET of surviving edges
 //                        is bit-exact --, stable compaction, component-pair key per edge;
 //   spg_spg_group_edges  stable sort by the component-pair key (graphs.py:121-125; inside a group the edges stay in (source,
 //                        target) order -- the reference's argsort leaves that order unspecified), run-length encoding -> superedges;
@@ -46,6 +46,26 @@ __device__ __forceinline__ unsigned ordered_bits(float f) {
   unsigned b = __float_as_uint(f);
   if (b == 0x80000000u) b = 0u;
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+// correctly rounded float32 square root, as np.sqrt of a float32 array returns it.  (__fsqrt_rn is NOT that here: without
+// OCML_BASIC_ROUNDED_OPERATIONS the HIP headers map it to the native instruction, good to one ulp.)  The float64 root is correctly
+// rounded and 53 >= 2 * 24 + 2 bits, so rounding it once more to float32 cannot differ from rounding the exact root.
+__device__ __forceinline__ float sqrt_rn_f32(float x) { return (float)sqrt((double)x); }
+
+// dx*dx + dy*dy (+ dz*dz) in float32, every product and every sum rounded on its own, added left to right -- what numpy does
+// with a float32 array.  (__fmul_rn / __fadd_rn do NOT guarantee that here: without OCML_BASIC_ROUNDED_OPERATIONS the HIP headers
+// define them as plain * and +, which the compiler contracts into fused multiply-adds.)
+__device__ __forceinline__ float sumsq2_rn_f32(float dx, float dy) {
+#pragma clang fp contract(off)
+  const float xx = dx * dx, yy = dy * dy;
+  return xx + yy;
+}
+__device__ __forceinline__ float sumsq3_rn_f32(float dx, float dy, float dz) {
+#pragma clang fp contract(off)
+  const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
+  const float xy = xx + yy;
+  return xy + zz;
 }
 
 // -------------------------------------------------------------------------------------------------------------------
@@ -93,8 +113,8 @@ __global__ void edge_flags_kernel(const u64* __restrict__ keys, long n, const fl
     const long a = (long)(k >> 32), b = (long)(k & 0xffffffffull);
     const float dx = __fsub_rn(xyz[3 * a], xyz[3 * b]), dy = __fsub_rn(xyz[3 * a + 1], xyz[3 * b + 1]),
                 dz = __fsub_rn(xyz[3 * a + 2], xyz[3 * b + 2]);
-    const float s = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-    keep = __fsqrt_rn(s) < d_max;
+    const float s = sumsq3_rn_f32(dx, dy, dz);
+    keep = sqrt_rn_f32(s) < d_max;
   }
   flags[i] = keep ? 1 : 0;
 }
@@ -223,10 +243,10 @@ __global__ __launch_bounds__(256) void superpoints_kernel(const float* __restric
         const float mean = __fdiv_rn(__fadd_rn(u, v), 2.f);
         centroids[3 * c + d] = mean;
         const float du = __fsub_rn(u, mean), dv = __fsub_rn(v, mean);
-        const float vd = __fdiv_rn(__fadd_rn(__fmul_rn(du, du), __fmul_rn(dv, dv)), 2.f);
+        const float vd = __fdiv_rn(sumsq2_rn_f32(du, dv), 2.f);
         var = d == 0 ? vd : __fadd_rn(var, vd);
       }
-      length[c] = __fsqrt_rn(var);
+      length[c] = sqrt_rn_f32(var);
       surface[c] = volume[c] = 0.f;
     }
     return;
@@ -297,7 +317,7 @@ __global__ __launch_bounds__(256) void superedges_kernel(const u64* __restrict__
     const float dx = __fsub_rn(xyz[3 * a], xyz[3 * t]), dy = __fsub_rn(xyz[3 * a + 1], xyz[3 * t + 1]),
                 dz = __fsub_rn(xyz[3 * a + 2], xyz[3 * t + 2]);      // delta is a float32 array in the reference (:193)
     sd[0] += (double)dx; sd[1] += (double)dy; sd[2] += (double)dz;
-    sn += (double)__fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+    sn += (double)sqrt_rn_f32(sumsq3_rn_f32(dx, dy, dz));
   }
   const double cnt = (double)(e - b);
   double mean[3];
