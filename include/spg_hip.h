@@ -388,6 +388,43 @@ int spg_xpart_weights(const int32_t* ends, long E, long n, const int32_t* pred_i
                       double factor, float* weights, int32_t* in_component, int32_t* component_size, int32_t* n_components,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* Evaluation of a predicted partition and the SEAL edge weights (supervized_partition/supervized_partition.py:248-375,
+ * partition/provider.py:689-695, learning/metrics.py:87-108, supervized_partition/losses.py:119-128 and :168-186);
+ * csrc/spg_parteval.hip.  n vertices in n_com components, E edges: 1 <= n, n_com < 2^31 - 1, 0 <= E < 2^30.  Integer atomics only:
+ * every output is the same from run to run.  error_flag (device int32) is OR-ed into, never cleared: bit 1 = a component id
+ * outside [0, n_com) (that vertex is left out), bit 2 = a negative value (spg_component_mode).
+ * spg_partition_index: in_component int32 [n] -> order int32 [n] (the vertices by component, ascending inside a component),
+ * offsets int32 [n_com + 1], size int32 [n_com]; an id no vertex carries is a component of size 0.
+ * spg_component_label_majority: labels uint32 [n, C + 1] (column 0 = unlabelled, left out), 1 <= C <= 64 -> sums int64 [n_com, C],
+ * label_com int32 [n_com] (first arg-max, 0 for an all-zero row), full_pred uint32 [n], confusion int64 [C, C] with
+ * confusion[:, label_com[c]] += sums[c, :] (overwritten, not accumulated).
+ * spg_component_mode: values int32 [n] >= 0 -> freq int32 [n_com] (count of the most frequent value), value int32 [n_com] (the
+ * smallest of the most frequent); an empty component: 0 and -1.
+ * spg_seal_weights: weights float32 [E] = float32(1 + double(max over both ends of size - freq) * factor) on transition edges,
+ * 1 elsewhere.
+ * spg_relax_edges: binary uint8 [E] -> relaxed uint8 [E] after `tolerance` rounds of "mark both ends of every set edge, then set
+ * edges from the marks".  mode 1 (symmetric): an edge is set if either end is marked.  mode 0: what the reference's function
+ * computes -- an edge is set if its TARGET is marked, edge 1 if any source is marked, edge 0 if any source is not (its uint8
+ * marks index the edge array as integers); needs E >= 2 when tolerance > 0.
+ * spg_pred_transition: out uint8 [E] = in_component[source] != in_component[target].
+ * spg_boundary_counts: a, b uint8 [E] -> counts int64 [2, 2], counts[a != 0][b != 0] (overwritten). */
+size_t spg_partition_index_workspace_bytes(long n, long n_com);
+int spg_partition_index(const int32_t* in_component, long n, long n_com, int32_t* order, int32_t* offsets, int32_t* size,
+                        int32_t* error_flag, void* workspace, size_t workspace_bytes, void* stream);
+int spg_component_label_majority(const uint32_t* labels, long n, int C, const int32_t* in_component, const int32_t* order, long n_com,
+                                 int64_t* sums, int32_t* label_com, uint32_t* full_pred, int64_t* confusion, void* stream);
+size_t spg_component_mode_workspace_bytes(long n, long n_com);
+int spg_component_mode(const int32_t* in_component, const int32_t* values, long n, long n_com, int32_t* freq, int32_t* value,
+                       int32_t* error_flag, void* workspace, size_t workspace_bytes, void* stream);
+int spg_seal_weights(const int32_t* ends, long E, long n, const int32_t* pred_in_component, const int32_t* component_size,
+                     const int32_t* component_freq, long n_com, const uint8_t* is_transition, double factor, float* weights,
+                     void* stream);
+size_t spg_relax_edges_workspace_bytes(long n);
+int spg_relax_edges(const int32_t* ends, long E, long n, const uint8_t* binary, int tolerance, int mode, uint8_t* relaxed,
+                    void* workspace, size_t workspace_bytes, void* stream);
+int spg_pred_transition(const int32_t* ends, long E, long n, const int32_t* in_component, uint8_t* out, void* stream);
+int spg_boundary_counts(const uint8_t* a, const uint8_t* b, long E, int64_t* counts, void* stream);
+
 /* Random streams of the loader generated on the device (optional; the default keeps numpy's streams on the host so
  * that seeded runs reproduce the reference's clouds): Philox4x32-10 keyed by (seed, superpoint id, step).  counts /
  * ids int64 [S], slot int32 [S] (row of the cloud tensor or -1) -> sample_idx int32 [S, npts] (spg.py:207-214), M

@@ -148,6 +148,16 @@ SIGNATURES = {
     'spg_connected_components': (_i, [_p, _p, _l, _l, _p, _p, _p, _p, _sz, _p]),
     'spg_xpart_workspace_bytes': (_sz, [_l, _l]),
     'spg_xpart_weights': (_i, [_p, _l, _l, _p, _p, ctypes.c_double, _p, _p, _p, _p, _p, _sz, _p]),
+    'spg_partition_index_workspace_bytes': (_sz, [_l, _l]),
+    'spg_partition_index': (_i, [_p, _l, _l, _p, _p, _p, _p, _p, _sz, _p]),
+    'spg_component_label_majority': (_i, [_p, _l, _i, _p, _p, _l, _p, _p, _p, _p, _p]),
+    'spg_component_mode_workspace_bytes': (_sz, [_l, _l]),
+    'spg_component_mode': (_i, [_p, _p, _l, _l, _p, _p, _p, _p, _sz, _p]),
+    'spg_seal_weights': (_i, [_p, _l, _l, _p, _p, _p, _l, _p, ctypes.c_double, _p, _p]),
+    'spg_relax_edges_workspace_bytes': (_sz, [_l]),
+    'spg_relax_edges': (_i, [_p, _l, _l, _p, _i, _i, _p, _p, _sz, _p]),
+    'spg_pred_transition': (_i, [_p, _l, _l, _p, _p, _p]),
+    'spg_boundary_counts': (_i, [_p, _p, _l, _p, _p]),
     'spg_edge_features': (_i, [ctypes.POINTER(EdgeFeatureSpecs), _p, _l, _p, _p, _p, _p]),
     'spg_loader_random': (_i, [_p, _p, _p, _i, _i, _i, ctypes.c_uint64, ctypes.c_uint32, _i, ctypes.c_float, _i, ctypes.c_float, _i, _p, _p, _p, _p]),
     'spg_cross_entropy_fwd': (_i, [_p, _p, _p, _i, _i, ctypes.c_int64, _i, _p, _p, _p, _p]),

@@ -99,3 +99,51 @@ class ConfusionMatrix:
 
     def count_gt(self, ground_truth):
         return self.confusion_matrix[ground_truth, :].sum()
+
+
+# ---- partition metrics of the learned partition (reference learning/metrics.py:87-108), computed by csrc/spg_parteval.hip ----
+def _indicator_counts(is_transition, pred_transitions):
+    from .. import ops
+    if not torch.cuda.is_available():
+        raise RuntimeError('superpoint_graph_amd.learning.metrics: the boundary metrics have no CPU path')
+    dev = torch.device('cuda', torch.cuda.current_device())
+
+    def up(a):
+        if torch.is_tensor(a):
+            a = a if a.dtype in (torch.bool, torch.uint8) else (a != 0)
+            return a.to(dev)
+        a = np.ascontiguousarray(a)
+        return ops.upload(torch.from_numpy(a if a.dtype in (np.bool_, np.uint8) else (a != 0)), dev)
+    return ops.boundary_counts(up(is_transition), up(pred_transitions)).cpu().numpy()
+
+
+def compute_boundary_recall(is_transition, pred_transitions):
+    """metrics.py:87-88 for 0 / 1 indicators: 100 * #(both set) / #(is_transition set), float64; 0 / 0 is NaN, as in numpy."""
+    c = _indicator_counts(is_transition, pred_transitions)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return np.float64(100 * c[1, 1]) / np.float64(c[1, 0] + c[1, 1])
+
+
+def compute_boundary_precision(is_transition, pred_transitions):
+    """metrics.py:91-92 for 0 / 1 indicators: 100 * #(both set) / #(pred_transitions set), float64; 0 / 0 is NaN."""
+    c = _indicator_counts(is_transition, pred_transitions)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return np.float64(100 * c[1, 1]) / np.float64(c[0, 1] + c[1, 1])
+
+
+def compute_OOA(components, labels, in_component=None):
+    """metrics.py:102-108: 100 * (sum over the components of the frequency of their most frequent hard label) / len(labels),
+    hard label = labels.argmax(1) over ALL columns, as there.  components: list of disjoint vertex index arrays; with
+    in_component (its membership vector) the list is only counted."""
+    from .. import ops
+    from ..partition.provider import _membership
+    if not torch.cuda.is_available():
+        raise RuntimeError('superpoint_graph_amd.learning.metrics: compute_OOA has no CPU path')
+    dev = torch.device('cuda', torch.cuda.current_device())
+    labels = np.asarray(labels)
+    hard = labels.argmax(1).astype(np.int32)
+    comp, n_com = _membership(components, len(labels), in_component)
+    index = ops.PartitionIndex(ops.upload(torch.from_numpy(comp), dev), n_com)
+    freq, _ = ops.component_mode(index, ops.upload(torch.from_numpy(hard), dev))
+    correct = np.int64(freq[:n_com - 1].sum().item())
+    return 100 * correct / len(labels)

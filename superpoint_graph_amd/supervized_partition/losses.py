@@ -1,12 +1,15 @@
-"""`zhang` / `compute_dist` / `compute_loss` / `compute_weights_XPART` / `compute_weight_loss` with the reference's signatures
-(supervized_partition/losses.py:24-166), computed by the HIP library (csrc/spg_edgeloss.hip through ops.EdgeGraph,
-ops.edge_dist, ops.edge_loss, ops.crosspartition_weights).  Everything between the embeddings and `loss.backward()` runs on the
-device: the distance and loss are one launch over the edges each, their backward is one launch over the vertices without
-atomics (deterministic), the cross-partition weights are a device connected-components pass and a sort.
+"""`zhang` / `compute_dist` / `compute_loss` / `compute_weights_XPART` / `compute_weights_SEAL` / `mode` / `relax_edge_binary` /
+`compute_weight_loss` with the reference's signatures (supervized_partition/losses.py:24-186), computed by the HIP library
+(csrc/spg_edgeloss.hip and csrc/spg_parteval.hip through ops.EdgeGraph, ops.edge_dist, ops.edge_loss,
+ops.crosspartition_weights, ops.seal_weights, ops.component_mode, ops.relax_edges).  Everything between the embeddings and
+`loss.backward()` runs on the device: the distance and loss are one launch over the edges each, their backward is one launch
+over the vertices without atomics (deterministic), the cross-partition weights are a device connected-components pass and a
+sort, the SEAL weights a sort of (component, object) pairs and one launch over the edges.
 
 What is not here: cut pursuit (`libcp`, losses.py:67-89 compute_partition).  The predicted partition is an INPUT:
 `compute_weight_loss(..., partition=(pred_components, pred_in_component))` takes what the caller's own cut pursuit returned.
-SEAL weights are not implemented.  No CPU path."""
+`relax_edge_binary` reproduces what the reference's function computes, including what its integer indexing does (see
+ops.relax_edges).  No CPU path."""
 from __future__ import annotations
 
 import numpy as np
@@ -108,13 +111,65 @@ def compute_weights_XPART(pred_components, pred_in_component, objects, edg_sourc
     return w.cpu().numpy()
 
 
+def _vertex_tensor(a, dev):
+    """A per-vertex integer array (numpy or tensor) as an int32 device tensor."""
+    if torch.is_tensor(a):
+        return a.to(device=dev, dtype=torch.int32)
+    return ops.upload(torch.from_numpy(np.ascontiguousarray(a).astype(np.int32)), dev)
+
+
+def compute_weights_SEAL(pred_components, pred_in_component, objects, edg_source, edg_target, is_transition, transition_factor):
+    """losses.py:119-128 -> float32 numpy [E], as the reference returns it: 1 + max over both ends of (size of the predicted
+    component - frequency of its most frequent object) * transition_factor on transition edges (float64, rounded once), 1
+    elsewhere.  Of pred_components only its length enters (the membership is pred_in_component)."""
+    n = len(pred_in_component)
+    g = _graph(edg_source, edg_target, n)
+    dev = g.device
+    index = ops.PartitionIndex(_vertex_tensor(pred_in_component, dev), len(pred_components))
+    tr = is_transition if torch.is_tensor(is_transition) else torch.from_numpy(np.ascontiguousarray(is_transition))
+    w = ops.seal_weights(g, index, _vertex_tensor(objects, dev), (tr != 0).to(device=dev, dtype=torch.uint8), transition_factor)
+    return w.cpu().numpy()
+
+
+def mode(array, only_frequency=False):
+    """losses.py:168-173: the most frequent value of a non-negative integer array (the smallest among equals) and its
+    frequency; only_frequency: the frequency alone."""
+    a = array.detach().cpu().numpy() if torch.is_tensor(array) else np.asarray(array)
+    a = a.reshape(-1)
+    if a.size == 0:
+        raise ValueError('mode: empty array')
+    if not np.issubdtype(a.dtype, np.integer) and a.dtype != np.bool_:
+        raise TypeError('mode: an integer array is expected')
+    if int(a.max()) > 2 ** 31 - 1:
+        raise ValueError('mode: values up to 2^31 - 1')
+    dev = _dev()
+    index = ops.PartitionIndex(torch.zeros(a.size, dtype=torch.int32, device=dev), 1)
+    freq, value = ops.component_mode(index, _vertex_tensor(a, dev))
+    freq = np.int64(freq.item())
+    if only_frequency:
+        return freq
+    return a.dtype.type(value.item()), freq
+
+
+def relax_edge_binary(edg_binary, edg_source, edg_target, n_ver, tolerance):
+    """losses.py:175-186 -> numpy [E] of the input's dtype (bool or uint8): what the reference's function computes, which is
+    not the symmetric relaxation its text describes (ops.relax_edges, mode 'reference': edges 0 and 1 are set through integer
+    indexing, the relaxation spreads through target vertices only).  E < 2 with tolerance > 0 raises ValueError."""
+    b = edg_binary.detach().cpu().numpy() if torch.is_tensor(edg_binary) else np.asarray(edg_binary)
+    if b.dtype not in (np.bool_, np.uint8):
+        raise TypeError(f'relax_edge_binary: a bool or uint8 indicator is expected, got {b.dtype}')
+    g = _graph(edg_source, edg_target, int(n_ver))
+    out = ops.relax_edges(g, ops.upload(torch.from_numpy(np.ascontiguousarray(b)), g.device), int(tolerance), 'reference')
+    return out.cpu().numpy()
+
+
 def compute_weight_loss(args, embeddings, objects, edg_source, edg_target, is_transition, diff, return_partition, xyz=0, partition=None):
     """losses.py:91-117.  partition = (pred_components, pred_in_component) of the caller's cut pursuit (needed by
-    loss_weight 'crosspartition' and by return_partition).  -> weights float32 [E] on the device [, pred_components,
+    loss_weight 'crosspartition' and 'seal' and by return_partition; 'seal' without it raises NotImplementedError).  -> weights float32 [E] on the device [, pred_components,
     pred_in_component]."""
-    if args.loss_weight == 'seal':
-        raise NotImplementedError('loss_weight seal (compute_weights_SEAL) is not implemented')
-    if args.loss_weight not in ('none', 'proportional', 'crosspartition'):
+    if args.loss_weight == 'seal' and partition is None:
+        raise NotImplementedError(_NO_LIBCP % "loss_weight 'seal'")
+    if args.loss_weight not in ('none', 'proportional', 'crosspartition', 'seal'):
         raise ValueError(" %s is an unknown argument of parameter --loss" % (args.loss_weight))
     if (args.loss_weight == 'crosspartition' or return_partition) and partition is None:
         raise ValueError(_NO_LIBCP % ("loss_weight 'crosspartition'" if args.loss_weight == 'crosspartition' else 'return_partition'))
@@ -131,6 +186,11 @@ def compute_weight_loss(args, embeddings, objects, edg_source, edg_target, is_tr
         weights_loss = torch.full((E,), intra, dtype=torch.float32, device=dev)
         if n_trans:
             weights_loss[trans] = float(E) / float(n_trans) * args.transition_factor
+    elif args.loss_weight == 'seal':
+        # :103: the SEAL weights of the given partition, with the plain transition factor
+        g = _graph(edg_source, edg_target, int(embeddings.shape[0]))
+        index = ops.PartitionIndex(_vertex_tensor(partition[1], dev), len(partition[0]))
+        weights_loss = ops.seal_weights(g, index, _vertex_tensor(objects, dev), (is_transition != 0).to(torch.uint8), args.transition_factor)
     else:
         pred_in_component = partition[1]
         g = _graph(edg_source, edg_target, int(embeddings.shape[0]))
