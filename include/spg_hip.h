@@ -683,6 +683,40 @@ int spg_prof_read_tag(int tag, double* ms, long* launches, double* flops);
 int spg_group_trace(void* buf, int max_launches);
 int spg_group_trace_read(int* out, int max);
 
+/* ---- batches of the learned partition on the device (csrc/spg_tiles.hip; reference supervized_partition/graph_processing.py:347-436
+ * graph_loader, :534-546 augment_cloud_whole, partition/ply_c/random_subgraph.cpp) ---- */
+#define SPG_TILES_VERTICES_PER_BLOCK 32
+/* The k-nearest-neighbour tiles of m selected vertices (graph_processing.py:389-411): xyz f32 [N, 3], rgb f32 [N, 3] or null,
+ * nei [N, K] int32 (nei_is_i64 = 0) or int64 indices into the full cloud, 1 <= k <= 64, k <= K; rows: ascending ids of the selected
+ * vertices [m], null = vertex i is row i (m <= N).  clouds f32 [m, F, k], F = 6 with cloud_rgb (needs rgb) else 3: (xyz[nei] - xyz[row])
+ * / (diameter + 1e-10f), then the neighbours' rgb; diameters f32 [m] = sqrt of the summed per-axis variances; clouds_global f32 [m, G] =
+ * diameter, then elevation[row] (elevation f32 [N] non-null), rgb[row] (own_rgb), xyn[row] (xyn f32 [N, 2] non-null), xyz[row, :2]
+ * (own_xy), in this order.  Bit for bit the float32 sequence numpy runs.  flags bit 0: non-temporal stores of clouds.  An index outside
+ * [0, N) in nei or rows sets bit 0 of *error_flag (device int32, zeroed by the caller) and is read as 0. */
+int spg_neighbourhood_tiles(const float* xyz, const float* rgb, long N, const void* nei, int nei_is_i64, long K, int k, const int64_t* rows,
+                            long m, int cloud_rgb, const float* elevation, const float* xyn, int own_rgb, int own_xy, int flags,
+                            float* clouds, float* clouds_global, float* diameters, int32_t* error_flag, void* stream);
+/* augment_cloud_whole with the random quantities as inputs: xyz_out = ((xyz - ref_point) @ M + ref_point) + noise_xyz, rgb_out =
+ * clip(rgb + noise_rgb, -1, 1).  M ([3, 3] row-major) and ref_point ([3]) are HOST pointers (both or neither); noise_* device f32
+ * [N, 3] or null; rgb_out may be null; without noise_rgb rgb_out is a copy. */
+int spg_augment_whole(const float* xyz, const float* rgb, long N, const float* M, const float* ref_point, const float* noise_xyz,
+                      const float* noise_rgb, float* xyz_out, float* rgb_out, void* stream);
+/* random_subgraph.cpp with the seed vertices as an explicit sequence (seeds: device int64 [n_seeds], consumed in order): rowptr / inc /
+ * ends of spg_edgegraph_build.  selected_ver u8 [n] in / out (zeros for a fresh selection), selected_edg u8 [E] out =
+ * selected[src] * selected[tgt]; state: device int64 [3] = {vertices selected so far (in / out), seeds consumed by this call (out),
+ * error word (out; 1 = a seed outside [0, n): nothing after it was consumed)}.  One workgroup; every loop is bounded by n. */
+size_t spg_random_subgraph_workspace_bytes(long n);
+int spg_random_subgraph(const int32_t* rowptr, const uint32_t* inc, const int32_t* ends, long E, long n, int subgraph_size,
+                        const int64_t* seeds, int n_seeds, uint8_t* selected_ver, uint8_t* selected_edg, int64_t* state, void* workspace,
+                        size_t workspace_bytes, void* stream);
+/* graph_processing.py:375-379: rows i64 [n] (the first counts[0]: the selected vertices, ascending), new_ver_index i64 [n] (-1 where
+ * unselected), kept_edges / edg_source / edg_target i64 [E] (the first counts[1]: the selected edge ids in order and their relabelled
+ * ends); counts: device int64 [2]. */
+size_t spg_induced_subgraph_workspace_bytes(long n, long E);
+int spg_induced_subgraph(const int32_t* ends, long E, long n, const uint8_t* selected_ver, const uint8_t* selected_edg, int64_t* rows,
+                         int64_t* new_ver_index, int64_t* kept_edges, int64_t* edg_source, int64_t* edg_target, int64_t* counts,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -158,6 +158,12 @@ SIGNATURES = {
     'spg_relax_edges': (_i, [_p, _l, _l, _p, _i, _i, _p, _p, _sz, _p]),
     'spg_pred_transition': (_i, [_p, _l, _l, _p, _p, _p]),
     'spg_boundary_counts': (_i, [_p, _p, _l, _p, _p]),
+    'spg_neighbourhood_tiles': (_i, [_p, _p, _l, _p, _i, _l, _i, _p, _l, _i, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p]),
+    'spg_augment_whole': (_i, [_p, _p, _l, _p, _p, _p, _p, _p, _p, _p]),
+    'spg_random_subgraph_workspace_bytes': (_sz, [_l]),
+    'spg_random_subgraph': (_i, [_p, _p, _p, _l, _l, _i, _p, _i, _p, _p, _p, _p, _sz, _p]),
+    'spg_induced_subgraph_workspace_bytes': (_sz, [_l, _l]),
+    'spg_induced_subgraph': (_i, [_p, _l, _l, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     'spg_edge_features': (_i, [ctypes.POINTER(EdgeFeatureSpecs), _p, _l, _p, _p, _p, _p]),
     'spg_loader_random': (_i, [_p, _p, _p, _i, _i, _i, ctypes.c_uint64, ctypes.c_uint32, _i, ctypes.c_float, _i, ctypes.c_float, _i, _p, _p, _p, _p]),
     'spg_cross_entropy_fwd': (_i, [_p, _p, _p, _i, _i, ctypes.c_int64, _i, _p, _p, _p, _p]),
