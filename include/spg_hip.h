@@ -163,6 +163,32 @@ int spg_pointnet_backward_ext(const spg_pointnet_cfg* cfg, int B, const float* c
                               const float* ext_transform, const void* const* params, const float* grad_emb, void* const* grads,
                               float* grad_transform, float* grad_global, void* workspace, void* bwd_workspace, void* stream);
 
+/* The PointNet of the learned partition's local embedder with GroupNorm instead of BatchNorm (learning/pointnet.py:24-49,
+ * 75-118 with norm = 'layer' (n_group = 1) or 'group'): cloud-resident kernels (spg_groupnorm.hip), no activation in HBM; train
+ * and eval are the same function and a cloud's result does not depend on the rest of the batch.  `net` must have nfeat_stn = 0
+ * (a stand-alone STN is such a net with nfeat = 2, nfeat_global = 0 and fc = [..., 4]); bn_eps / bn_momentum are ignored.
+ * Supported: 1 <= npts <= 64, nfeat <= 16, every width <= 128 (any value), n_group divides every normalised width, and an LDS
+ * layout that fits a compute unit; anything else returns -2 and spg_last_error() names the limit.
+ * Parameter groups: {weight, bias, norm.weight, norm.bias, NULL, NULL} per layer, convolutions then FCs.
+ * ext_transform [B, 4] = T - I or NULL (no transform).  What the forward leaves in `workspace` is per cloud only (statistics,
+ * pooled values, arg-max points).  Backward: grad_transform [B, 4], grad_global [B, nfeat_global] and grad_clouds
+ * [B, nfeat, npts] (wrt the clouds as given, the transform included) are optional outputs; the parameter gradients are summed
+ * from per-wavefront partials in a fixed order (no atomics). */
+typedef struct spg_gn_cfg {
+  spg_pointnet_cfg net;
+  int n_group;
+  float eps;
+} spg_gn_cfg;
+
+int spg_gn_check(const spg_gn_cfg* cfg);      /* 0, or -2 with the refused limit in spg_last_error() */
+size_t spg_gn_workspace_bytes(const spg_gn_cfg* cfg, int B);
+size_t spg_gn_bwd_workspace_bytes(const spg_gn_cfg* cfg, int B);
+int spg_gn_forward_ext(const spg_gn_cfg* cfg, int B, const float* clouds, const float* clouds_global, const float* ext_transform,
+                       const void* const* params, float* emb, void* workspace, void* stream);
+int spg_gn_backward_ext(const spg_gn_cfg* cfg, int B, const float* clouds, const float* clouds_global, const float* ext_transform,
+                        const void* const* params, const float* grad_emb, void* const* grads, float* grad_transform,
+                        float* grad_global, float* grad_clouds, void* workspace, void* bwd_workspace, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * RNN-ECC module = RNNGraphConvModule.forward (learning/modules.py:152-183) with a GRUCellEx or LSTMCellEx cell:
  * filter-generating MLP on the edge features (learning/graphnet.py:17-34, once per forward), then

@@ -30,6 +30,11 @@ class PointNetCfg(ctypes.Structure):
                 ('last_ac', ctypes.c_int), ('bn_eps', ctypes.c_float), ('bn_momentum', ctypes.c_float)]
 
 
+class GnCfg(ctypes.Structure):
+    """spg_gn_cfg of include/spg_hip.h (the GroupNorm / LayerNorm PointNet of the local embedder)."""
+    _fields_ = [('net', PointNetCfg), ('n_group', ctypes.c_int), ('eps', ctypes.c_float)]
+
+
 class EccRnnCfg(ctypes.Structure):
     _fields_ = [('nc', ctypes.c_int), ('nrepeats', ctypes.c_int), ('matrix', ctypes.c_int), ('layernorm', ctypes.c_int),
                 ('ingate', ctypes.c_int), ('cat_all', ctypes.c_int), ('n_fnet', ctypes.c_int),
@@ -100,6 +105,11 @@ SIGNATURES = {
     'spg_pointnet_debug_offset': (_l, [ctypes.POINTER(PointNetCfg), _i, _i, _i, _i]),
     'spg_pointnet_bwd_workspace_bytes': (_sz, [ctypes.POINTER(PointNetCfg), _i]),
     'spg_pointnet_backward': (_i, [ctypes.POINTER(PointNetCfg), _i, _p, _p, c_void_pp, _p, c_void_pp, _p, _p, _p]),
+    'spg_gn_check': (_i, [ctypes.POINTER(GnCfg)]),
+    'spg_gn_workspace_bytes': (_sz, [ctypes.POINTER(GnCfg), _i]),
+    'spg_gn_bwd_workspace_bytes': (_sz, [ctypes.POINTER(GnCfg), _i]),
+    'spg_gn_forward_ext': (_i, [ctypes.POINTER(GnCfg), _i, _p, _p, _p, c_void_pp, _p, _p, _p]),
+    'spg_gn_backward_ext': (_i, [ctypes.POINTER(GnCfg), _i, _p, _p, _p, c_void_pp, _p, c_void_pp, _p, _p, _p, _p, _p, _p]),
     'spg_eccrnn_workspace_bytes': (_sz, [ctypes.POINTER(EccRnnCfg), _i, _i, _i]),
     'spg_eccrnn_forward': (_i, [ctypes.POINTER(EccRnnCfg), _i, _i, _p, _p, _p, c_void_pp, _p, _p, _i, _i, _p]),
     'spg_eccrnn_bwd_workspace_bytes': (_sz, [ctypes.POINTER(EccRnnCfg), _i, _i]),

@@ -12,19 +12,48 @@ from .. import ops
 
 
 def _seq_groups(seq):
-    """(weight, bias, bn.weight, bn.bias, running_mean, running_var) per parametric layer of a
-    Sequential[Conv1d|Linear, (BatchNorm1d), ReLU, ...]."""
+    """(weight, bias, norm.weight, norm.bias, running_mean, running_var) per parametric layer of a
+    Sequential[Conv1d|Linear, (BatchNorm1d|GroupNorm), ReLU, ...]."""
     groups, mods = [], list(seq)
     i = 0
     while i < len(mods):
         m = mods[i]
         if isinstance(m, (nn.Conv1d, nn.Linear)):
-            bn = mods[i + 1] if i + 1 < len(mods) and isinstance(mods[i + 1], nn.BatchNorm1d) else None
+            bn = mods[i + 1] if i + 1 < len(mods) and isinstance(mods[i + 1], (nn.BatchNorm1d, nn.GroupNorm)) else None
             groups.append((m, bn))
-        elif not isinstance(m, (nn.BatchNorm1d, nn.ReLU, nn.Dropout)):
-            raise NotImplementedError(f'{type(m).__name__} is not supported by the HIP PointNet (norm must be "batch")')
+        elif not isinstance(m, (nn.BatchNorm1d, nn.GroupNorm, nn.ReLU, nn.Dropout)):
+            raise NotImplementedError(f'{type(m).__name__} is not supported by the HIP PointNet (norm must be "batch", "layer" or "group")')
         i += 1
     return groups
+
+
+def _norm_module(norm, n_group, width):
+    """The normalisation the reference puts behind a layer of `width` channels (learning/pointnet.py:30-35)."""
+    if norm == 'batch':
+        return nn.BatchNorm1d(width)
+    if norm == 'layer':
+        return nn.GroupNorm(1, width)
+    if norm == 'group':
+        return nn.GroupNorm(n_group, width)
+    raise ValueError(f'norm must be "batch", "layer" or "group", got {norm!r}')
+
+
+def _groupnorm_spec(*modules):
+    """None for BatchNorm networks; (n_group, eps) when every normalisation of `modules` is a GroupNorm with one group count.
+    A mix of BatchNorm and GroupNorm, or GroupNorms that differ, are refused: no kernel covers them."""
+    norms = [m for mod in modules for m in mod.modules() if isinstance(m, (nn.BatchNorm1d, nn.GroupNorm))]
+    gns = [m for m in norms if isinstance(m, nn.GroupNorm)]
+    if not gns:
+        return None
+    if len(gns) != len(norms):
+        raise NotImplementedError('a mix of BatchNorm and GroupNorm in one model is not implemented on the HIP path '
+                                  '(build the STN and the PointNet with the same `norm`)')
+    spec = {(m.num_groups, m.eps) for m in gns}
+    if len(spec) != 1:
+        raise NotImplementedError(f'GroupNorm layers with different (num_groups, eps) {sorted(spec)} are not implemented on the HIP path')
+    if any(not m.affine for m in gns):
+        raise NotImplementedError('GroupNorm(affine=False) is not implemented on the HIP path')
+    return spec.pop()
 
 
 def _bn_momentum(bn):
@@ -40,7 +69,7 @@ def _bn_momentum(bn):
 def _tensors(lin, bn):
     w = lin.weight
     return (w, lin.bias, None if bn is None else bn.weight, None if bn is None else bn.bias,
-            None if bn is None else bn.running_mean, None if bn is None else bn.running_var)
+            getattr(bn, 'running_mean', None), getattr(bn, 'running_var', None))
 
 
 class STNkD(nn.Module):
@@ -50,18 +79,16 @@ class STNkD(nn.Module):
 
     def __init__(self, nfeat, nf_conv, nf_fc, K=2, norm='batch', affine=True, n_group=1):
         super(STNkD, self).__init__()
-        if norm != 'batch':
-            raise NotImplementedError('only norm="batch" is implemented on the HIP path')
         modules = []
         for i in range(len(nf_conv)):
             modules.append(nn.Conv1d(nf_conv[i - 1] if i > 0 else nfeat, nf_conv[i], 1))
-            modules.append(nn.BatchNorm1d(nf_conv[i]))
+            modules.append(_norm_module(norm, n_group, nf_conv[i]))
             modules.append(nn.ReLU(True))
         self.convs = nn.Sequential(*modules)
         modules = []
         for i in range(len(nf_fc)):
             modules.append(nn.Linear(nf_fc[i - 1] if i > 0 else nf_conv[-1], nf_fc[i]))
-            modules.append(nn.BatchNorm1d(nf_fc[i]))
+            modules.append(_norm_module(norm, n_group, nf_fc[i]))
             modules.append(nn.ReLU(True))
         self.fcs = nn.Sequential(*modules)
         self.proj = nn.Linear(nf_fc[-1], K * K)
@@ -90,11 +117,18 @@ class STNkD(nn.Module):
         return ops.make_pointnet_cfg(self._nfeat, 0, 0, npts, [], [], self._nf_conv, self._nf_fc + [self._K * self._K], False,
                                      bn0.eps, _bn_momentum(bn0))
 
+    def _gn_cfg(self, npts):
+        n_group, eps = _groupnorm_spec(self)
+        return ops.make_gn_cfg(self._nfeat, 0, npts, self._nf_conv, self._nf_fc + [self._K * self._K], n_group, eps)
+
     def forward(self, input):
         """[B, nfeat, P] -> [B, K, K] transformation matrices (reference learning/pointnet.py:55-61)."""
         if not input.is_cuda:
             raise RuntimeError('superpoint_graph_amd.STNkD has no CPU path; move the module and inputs to the GPU')
         self.eye = self.eye.to(input.device)
+        if _groupnorm_spec(self) is not None:      # norm = 'layer' | 'group': the cloud-resident kernels (spg_groupnorm.hip)
+            out = _GroupNormFunction.apply(self, input.contiguous().float(), None, None, *self._flat_params())
+            return out.view(-1, self.eye.size(1), self.eye.size(2)) + self.eye
         if self.training:
             nbt = [m.num_batches_tracked for m in self.modules() if isinstance(m, nn.BatchNorm1d)]
             torch._foreach_add_(nbt, 1)
@@ -167,6 +201,32 @@ class _PointNetFunction(torch.autograd.Function):
         return (None, None, None, None, None) + tuple(flat)
 
 
+class _GroupNormFunction(torch.autograd.Function):
+    """A GroupNorm / LayerNorm network without inner STN (a stand-alone STNkD, or a PointNet with nfeat_stn = 0) through
+    spg_gn_forward_ext / spg_gn_backward_ext: differentiable wrt the clouds, the global features, the externally computed
+    2x2 matrices `T` (None: no transform) and the parameters.  Train and eval are the same function."""
+
+    @staticmethod
+    def forward(ctx, module, clouds, clouds_global, T, *flat_params):
+        groups = module._groups_tensors()
+        ext = None
+        if T is not None:
+            ext = T.reshape(-1, 4) - torch.eye(2, device=T.device, dtype=T.dtype).reshape(1, 4)
+        out, state = ops.gn_forward(module._gn_cfg(clouds.shape[2]), clouds, clouds_global, groups, ext_transform=ext)
+        ctx.state, ctx.groups, ctx.glob_shape = state, groups, None if clouds_global is None else clouds_global.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        gg, g_T, g_glob, g_clouds = ops.gn_backward(ctx.state, ctx.groups, grad_out, want_clouds=ctx.needs_input_grad[1])
+        if g_T is not None:
+            g_T = g_T.view(-1, 2, 2)
+        if g_glob is not None:
+            g_glob = g_glob.view(ctx.glob_shape)
+        flat = [g for row in gg for g in row if g is not None]
+        return (None, g_clouds, g_glob, g_T) + tuple(flat)
+
+
 class _LocalPointNetFunction(torch.autograd.Function):
     """PointNet WITHOUT inner STN whose xy channels are transformed by externally computed 2x2 matrices, differentiable
     wrt those matrices and wrt the global features (what LocalCloudEmbedder.run_batch composes, learning/pointnet.py:188-205)."""
@@ -201,8 +261,6 @@ class PointNet(nn.Module):
     def __init__(self, nf_conv, nf_fc, nf_conv_stn, nf_fc_stn, nfeat, nfeat_stn=2, nfeat_global=1, prelast_do=0.5,
                  last_ac=False, is_res=False, norm='batch', affine=True, n_group=1, last_bn=False):
         super(PointNet, self).__init__()
-        if norm != 'batch':
-            raise NotImplementedError('only norm="batch" is implemented on the HIP path')
         torch.manual_seed(0)          # reference learning/pointnet.py:78
         if nfeat_stn > 0:
             self.stn = STNkD(nfeat_stn, nf_conv_stn, nf_fc_stn, norm=norm, n_group=n_group)
@@ -210,14 +268,14 @@ class PointNet(nn.Module):
         modules = []
         for i in range(len(nf_conv)):
             modules.append(nn.Conv1d(nf_conv[i - 1] if i > 0 else nfeat, nf_conv[i], 1))
-            modules.append(nn.BatchNorm1d(nf_conv[i]))
+            modules.append(_norm_module(norm, n_group, nf_conv[i]))
             modules.append(nn.ReLU(True))
         self.convs = nn.Sequential(*modules)
         modules = []
         for i in range(len(nf_fc)):
             modules.append(nn.Linear(nf_fc[i - 1] if i > 0 else nf_conv[-1] + nfeat_global, nf_fc[i]))
             if i < len(nf_fc) - 1 or last_ac:
-                modules.append(nn.BatchNorm1d(nf_fc[i]))
+                modules.append(_norm_module(norm, n_group, nf_fc[i]))
                 modules.append(nn.ReLU(True))
             if i == len(nf_fc) - 2 and prelast_do > 0:
                 modules.append(nn.Dropout(prelast_do))
@@ -256,6 +314,22 @@ class PointNet(nn.Module):
                                                 self._nf_conv, self._nf_fc, self._last_ac, bn0.eps, _bn_momentum(bn0))
         return cache[npts]
 
+    def _gn_spec(self):
+        """None for a BatchNorm model, else (n_group, eps); refuses what the GroupNorm kernels do not cover."""
+        if '_gn_spec_cache' in self.__dict__:      # the module structure is fixed after construction (as layer_groups assumes)
+            return self.__dict__['_gn_spec_cache']
+        spec = _groupnorm_spec(self)
+        if spec is not None and self.nfeat_stn > 0:
+            raise NotImplementedError('a GroupNorm / LayerNorm PointNet with an inner STN (nfeat_stn > 0, CloudEmbedder) is not implemented '
+                                      'on the HIP path: the reference has --ptn_norm for the local embedder only (LocalCloudEmbedder: '
+                                      'a stand-alone model.stn and a model.ptn with nfeat_stn = 0)')
+        self.__dict__['_gn_spec_cache'] = spec
+        return spec
+
+    def _gn_cfg(self, npts):
+        n_group, eps = self._gn_spec()
+        return ops.make_gn_cfg(self._nfeat, self._nfeat_global, npts, self._nf_conv, self._nf_fc, n_group, eps, self._last_ac)
+
     def _bump_batches_tracked(self, times):
         nbt = self.__dict__.get('_nbt_cache')
         if nbt is None:
@@ -272,6 +346,8 @@ class PointNet(nn.Module):
         if self.nfeat_stn > 0 and self.stn._K != 2:
             raise NotImplementedError('the fused STN applies a 2x2 transform (K=2), as PointNet.forward does')
         input = input.contiguous().float()
+        if self._gn_spec() is not None:      # norm = 'layer' | 'group': the cloud-resident kernels (spg_groupnorm.hip)
+            return _GroupNormFunction.apply(self, input, input_global, None, *self._flat_params())
         if self.training:
             self._bump_batches_tracked(bn_update_times)
         if getattr(self, '_spg_direct_grads', False) and torch.is_grad_enabled():
@@ -289,7 +365,8 @@ class LocalCloudEmbedder():
     2x2 transform is applied by the first convolution while it stages the cloud.  The kernels have no chunk limit, but the
     reference's chunks are OBSERVABLE in training mode (every chunk is its own BatchNorm batch: own statistics, own
     running-stat update), so training-mode batches above 2^16 - 1 clouds are processed in the same chunks; in eval mode
-    (running statistics) the whole batch is one launch sequence."""
+    (running statistics) the whole batch is one launch sequence.  A GroupNorm / LayerNorm model (--ptn_norm layer|group) has no
+    batch statistics: its chunks are unobservable, so the whole batch is one launch sequence in training mode too."""
 
     CHUNK = 2 ** 16 - 1      # learning/pointnet.py:193
 
@@ -301,7 +378,7 @@ class LocalCloudEmbedder():
         if not clouds.is_cuda:
             raise RuntimeError('superpoint_graph_amd.LocalCloudEmbedder has no CPU path')
         n = clouds.shape[0]
-        if n > self.CHUNK and (model.ptn.training or (self.nfeat_stn > 0 and model.stn.training)):
+        if n > self.CHUNK and model.ptn._gn_spec() is None and (model.ptn.training or (self.nfeat_stn > 0 and model.stn.training)):
             # the reference's order: all STN chunks, then all PointNet chunks (:196-198, :204-206); the two networks share no
             # BatchNorm layer, so chunk-by-chunk evaluation of the pair gives the same statistics and updates
             clouds_global = clouds_global.reshape(n, -1)
@@ -315,6 +392,11 @@ class LocalCloudEmbedder():
             raise ValueError('LocalCloudEmbedder expects model.ptn without an inner STN (nfeat_stn = 0) and a separate model.stn')
         clouds = clouds.contiguous().float()
         clouds_global = clouds_global.float().reshape(clouds.shape[0], -1)
+        if ptn._gn_spec() is not None:
+            return self._run_groupnorm(model, clouds, clouds_global)
+        if self.nfeat_stn > 0 and _groupnorm_spec(model.stn) is not None:
+            raise NotImplementedError('a mix of BatchNorm and GroupNorm in one model is not implemented on the HIP path '
+                                      '(model.stn is GroupNorm, model.ptn is BatchNorm)')
         if self.nfeat_stn > 0:
             T = model.stn(clouds[:, :self.nfeat_stn, :].contiguous())
             if self.stn_as_global:
@@ -325,6 +407,25 @@ class LocalCloudEmbedder():
             out = _LocalPointNetFunction.apply(ptn, clouds, clouds_global.contiguous(), T, ptn.training, *extra)
         else:
             out = ptn(clouds, clouds_global.contiguous())
+        return nn.functional.normalize(out)
+
+    def _run_groupnorm(self, model, clouds, clouds_global):
+        """The same composition (learning/pointnet.py:195-207) on the cloud-resident GroupNorm kernels: the transform is applied
+        while a cloud is staged, and the gradient flows back into T through the transform and through `stn_as_global`."""
+        ptn, T = model.ptn, None
+        if ptn.training and ptn._prelast_do > 0:
+            raise NotImplementedError('ptn_prelast_do > 0 (dropout before the last layer) is not implemented on the HIP path')
+        if self.nfeat_stn > 0:
+            # (the two networks may differ in their group count: the reference's create_model hands ptn_n_group to the STN only)
+            if _groupnorm_spec(model.stn) is None:
+                raise NotImplementedError('a mix of BatchNorm and GroupNorm in one model is not implemented on the HIP path '
+                                          '(model.stn is BatchNorm, model.ptn is GroupNorm)')
+            if self.nfeat_stn != 2 or model.stn._K != 2:
+                raise NotImplementedError('the GroupNorm local embedder applies a 2x2 transform to the xy rows (ptn_nfeat_stn = 2, K = 2)')
+            T = model.stn(clouds[:, :2, :].contiguous())
+            if self.stn_as_global:
+                clouds_global = torch.cat([clouds_global, T.reshape(-1, 4)], 1)
+        out = _GroupNormFunction.apply(ptn, clouds, clouds_global.contiguous(), T, *ptn._flat_params())
         return nn.functional.normalize(out)
 
     def run_batch_cpu(self, model, clouds, clouds_global, *excess):

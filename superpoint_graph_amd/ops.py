@@ -9,7 +9,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import _lib
-from ._lib import EccRnnCfg, PointNetCfg, check, lib
+from ._lib import EccRnnCfg, GnCfg, PointNetCfg, check, lib
 
 
 def _stream() -> int:
@@ -385,6 +385,86 @@ def pointnet_backward(state: PointNetState, groups, grad_emb, out_grads=None, wa
     if want_input_grads:
         return gg, g_T, g_glob
     return gg
+
+
+# --------------------------------------------------------------------------------------------------
+# GroupNorm / LayerNorm PointNet (the learned partition's local embedder with --ptn_norm layer|group)
+# --------------------------------------------------------------------------------------------------
+def _gn_check(rc: int, what: str):
+    """-2 is the library's "outside the supported range": a NotImplementedError that names the limit."""
+    if rc == -2:
+        raise NotImplementedError(lib().spg_last_error().decode())
+    check(rc, what)
+
+
+def make_gn_cfg(nfeat, nfeat_global, npts, conv, fc, n_group, eps=1e-5, last_ac=False) -> GnCfg:
+    """spg_gn_cfg of a PointNet without inner STN (a stand-alone STN: nfeat_global = 0, fc = [..., K * K]); raises
+    NotImplementedError for what the kernels do not cover, before anything is launched."""
+    if len(conv) > _lib.SPG_MAX_LAYERS or len(fc) > _lib.SPG_MAX_LAYERS:
+        raise NotImplementedError(f'GroupNorm PointNet: at most SPG_MAX_LAYERS = {_lib.SPG_MAX_LAYERS} layers per stack')
+    c = GnCfg()
+    c.net = make_pointnet_cfg(nfeat, 0, nfeat_global, npts, [], [], conv, fc, last_ac, eps, 0.0)
+    c.n_group, c.eps = int(n_group), float(eps)
+    _gn_check(lib().spg_gn_check(ctypes.byref(c)), 'spg_gn_check')
+    return c
+
+
+class GroupNormState:
+    """What a forward leaves for its backward: per cloud only (statistics, pooled values, arg-max points)."""
+
+    def __init__(self, cfg, B, clouds, clouds_global, ws, ext_transform):
+        self.cfg, self.B, self.clouds, self.clouds_global, self.ws, self.ext_transform = cfg, B, clouds, clouds_global, ws, ext_transform
+
+
+def gn_forward(cfg: GnCfg, clouds, clouds_global, groups, ext_transform=None):
+    """groups: one 6-tuple (weight, bias, norm.weight, norm.bias, None, None) per layer, convolutions then FCs.
+    ext_transform: [B, 4] = T - I or None.  Returns (out [B, D], GroupNormState); train and eval are the same function."""
+    _req(clouds, torch.float32, 'clouds')
+    net, B = cfg.net, clouds.shape[0]
+    if clouds.shape[1] != net.nfeat or clouds.shape[2] != net.npts:
+        raise ValueError(f'clouds must be [B, {net.nfeat}, {net.npts}], got {tuple(clouds.shape)}')
+    D = net.fc[net.n_fc - 1]
+    if clouds_global is not None:
+        clouds_global = _req(clouds_global.reshape(B, -1).contiguous(), torch.float32, 'clouds_global')
+        if clouds_global.shape[1] != net.nfeat_global:
+            raise ValueError('clouds_global width does not match nfeat_global')
+    elif net.nfeat_global != 0:
+        raise ValueError('clouds_global is required')
+    if ext_transform is not None:
+        ext_transform = _req(ext_transform.reshape(B, 4).contiguous(), torch.float32, 'ext_transform')
+    if B == 0:
+        return torch.zeros(0, D, dtype=torch.float32, device=clouds.device), GroupNormState(cfg, 0, clouds, clouds_global, None, ext_transform)
+    nbytes = lib().spg_gn_workspace_bytes(ctypes.byref(cfg), B)
+    if nbytes == 0:
+        _gn_check(lib().spg_gn_check(ctypes.byref(cfg)), 'spg_gn_workspace_bytes')
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=clouds.device)
+    emb = torch.empty(B, D, dtype=torch.float32, device=clouds.device)
+    flat = [t for g in groups for t in g]
+    _gn_check(lib().spg_gn_forward_ext(ctypes.byref(cfg), B, _ptr(clouds), _ptr(clouds_global), _ptr(ext_transform), _ptr_array(flat),
+                                       _ptr(emb), _ptr(ws), _stream()), 'spg_gn_forward_ext')
+    return emb, GroupNormState(cfg, B, clouds, clouds_global, ws, ext_transform)
+
+
+def gn_backward(state: GroupNormState, groups, grad_emb, want_clouds=False):
+    """-> (list of (d weight, d bias, d norm.weight, d norm.bias) per layer, grad wrt the transform [B, 4] or None, grad wrt the
+    global features or None, grad wrt the clouds or None).  Bit-reproducible: partials in a fixed layout, summed in a fixed order."""
+    cfg, B = state.cfg, state.B
+    grad_emb = _req(grad_emb.contiguous(), torch.float32, 'grad_emb')
+    dev = grad_emb.device
+    gg = [tuple(None if g[k] is None else torch.empty_like(g[k]) for k in range(4)) for g in groups]
+    g_T = torch.empty(B, 4, dtype=torch.float32, device=dev) if state.ext_transform is not None else None
+    g_glob = torch.empty_like(state.clouds_global) if state.clouds_global is not None else None
+    g_clouds = torch.empty_like(state.clouds) if want_clouds else None
+    if B == 0:
+        return [tuple(None if t is None else t.zero_() for t in row) for row in gg], g_T, g_glob, g_clouds
+    nbytes = lib().spg_gn_bwd_workspace_bytes(ctypes.byref(cfg), B)
+    bws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    flat = [t for g in groups for t in g]
+    flatg = [t for row in gg for t in list(row) + [None, None]]
+    _gn_check(lib().spg_gn_backward_ext(ctypes.byref(cfg), B, _ptr(state.clouds), _ptr(state.clouds_global), _ptr(state.ext_transform),
+                                        _ptr_array(flat), _ptr(grad_emb), _ptr_array(flatg), _ptr(g_T), _ptr(g_glob), _ptr(g_clouds),
+                                        _ptr(state.ws), _ptr(bws), _stream()), 'spg_gn_backward_ext')
+    return gg, g_T, g_glob, g_clouds
 
 
 # --------------------------------------------------------------------------------------------------
