@@ -23,44 +23,15 @@
 //   (min, max) component key per transition edge -> radix sort + run lengths -> w = 1 + min(size) / count * factor in float64.
 #include <climits>
 #include <cstring>
-#include <rocprim/rocprim.hpp>
 
 #include "../../include/spg_hip.h"
-#include "spg_common.h"
+#include "spg_part.h"
 
 namespace {
-
-typedef unsigned long long u64;
-
-#define SPG_RP(expr)                                                                      \
-  do {                                                                                    \
-    hipError_t e__ = (expr);                                                              \
-    if (e__ != hipSuccess) {                                                              \
-      spg_set_error("%s:%d: %s: %s", __FILE__, __LINE__, #expr, hipGetErrorString(e__));  \
-      return (int)e__;                                                                    \
-    }                                                                                     \
-  } while (0)
 
 constexpr int EL_BLOCK = 256;
 constexpr int CC_MAX_ROUNDS = 32;      // link + jump rounds; one round completes the forest, the next one confirms it
 constexpr int CC_JUMP = 32;            // ancestors a lane follows per jump pass
-
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-inline size_t max2(size_t a, size_t b) { return a > b ? a : b; }
-inline int bits_of(unsigned long v) { int b = 1; while (b < 64 && (v >> b) != 0) ++b; return b; }
-
-struct Carve {
-  char* p;
-  size_t left;
-  bool ok = true;
-  void* take(size_t bytes) {
-    bytes = align256(bytes);
-    if (bytes > left) { ok = false; return nullptr; }
-    void* r = p;
-    p += bytes; left -= bytes;
-    return r;
-  }
-};
 
 // -------------------------------------------------------------------------------------------------------------------
 // edge graph
@@ -94,11 +65,15 @@ __global__ void eg_rowptr_kernel(const unsigned* __restrict__ keys, long m, long
   rowptr[v] = (int32_t)lo;
 }
 
-size_t sort32_tmp(long m) {
-  size_t b = 0;
-  (void)rocprim::radix_sort_pairs(nullptr, b, (unsigned*)nullptr, (unsigned*)nullptr, (unsigned*)nullptr, (unsigned*)nullptr, (size_t)m, 0, 32, (hipStream_t)0);
-  return b;
-}
+struct EdgeGraphWs {      // incidences: keys in / out, values in; rocPRIM scratch
+  unsigned *k0, *k1, *v0;
+  void* tmp; size_t tmp_bytes;
+  EdgeGraphWs(Carve& w, long E) {
+    k0 = w.take_n<unsigned>(2 * E); k1 = w.take_n<unsigned>(2 * E); v0 = w.take_n<unsigned>(2 * E);
+    tmp_bytes = radix_sort_pairs_bytes<unsigned, unsigned>(2 * std::max<long>(E, 1), 0, 32);
+    tmp = w.take(tmp_bytes);
+  }
+};
 
 // -------------------------------------------------------------------------------------------------------------------
 // forward
@@ -352,24 +327,27 @@ __global__ void cc_label_kernel(const int* __restrict__ parent, const unsigned* 
   if (v == 0) *n_components = (int32_t)rank[n];
 }
 
-size_t scan_tmp(long m) {
-  size_t b = 0;
-  (void)rocprim::exclusive_scan(nullptr, b, (unsigned*)nullptr, (unsigned*)nullptr, 0u, (size_t)m, rocprim::plus<unsigned>(), (hipStream_t)0);
-  return b;
-}
+struct CcWs {
+  int *changed, *parent;
+  unsigned *isroot, *rank;
+  void* tmp; size_t tmp_bytes;
+  CcWs(Carve& w, long n) {
+    changed = (int*)w.take(256);
+    parent = w.take_n<int>(n);
+    isroot = w.take_n<unsigned>(n + 1);
+    rank = w.take_n<unsigned>(n + 1);
+    tmp_bytes = exclusive_scan_bytes<unsigned>(n + 1);
+    tmp = w.take(tmp_bytes);
+  }
+};
 
-size_t cc_bytes(long n) { return align256(256) + align256((size_t)n * 4) + 2 * align256((size_t)(n + 1) * 4) + align256(scan_tmp(n + 1)); }
-
+// (the caller has carved and checked ws)
 int cc_run(const int2* ends, const uint8_t* active, long E, long n, int32_t* in_component, int32_t* component_size, int32_t* n_components,
-           void* ws, size_t ws_bytes, hipStream_t st) {
-  Carve w{(char*)ws, ws_bytes};
-  int* changed = (int*)w.take(256);
-  int* parent = (int*)w.take((size_t)n * 4);
-  unsigned* isroot = (unsigned*)w.take((size_t)(n + 1) * 4);
-  unsigned* rank = (unsigned*)w.take((size_t)(n + 1) * 4);
-  size_t tmp_bytes = scan_tmp(n + 1);
-  void* tmp = w.take(tmp_bytes);
-  SPG_CHECK_ARG(w.ok, "workspace too small (spg_cc_workspace_bytes)");
+           const CcWs& ws, hipStream_t st) {
+  int *changed = ws.changed, *parent = ws.parent;
+  unsigned *isroot = ws.isroot, *rank = ws.rank;
+  void* tmp = ws.tmp;
+  size_t tmp_bytes = ws.tmp_bytes;
   const dim3 block(EL_BLOCK), gv(spg_cdiv(n, EL_BLOCK)), ge(spg_cdiv(std::max<long>(E, 1), EL_BLOCK));
   hipLaunchKernelGGL(cc_init_kernel, gv, block, 0, st, parent, n);
   SPG_LAUNCH_CHECK();
@@ -446,16 +424,27 @@ __global__ void xp_weights_kernel(const int2* __restrict__ ends, const int32_t* 
   weights[e] = w;
 }
 
-size_t sort64_tmp(long m) {
-  size_t b = 0;
-  (void)rocprim::radix_sort_keys(nullptr, b, (u64*)nullptr, (u64*)nullptr, (size_t)m, 0, 64, (hipStream_t)0);
-  return b;
-}
-size_t rle_tmp(long m) {
-  size_t b = 0;
-  (void)rocprim::run_length_encode(nullptr, b, (u64*)nullptr, (unsigned)m, (u64*)nullptr, (unsigned*)nullptr, (unsigned*)nullptr, (hipStream_t)0);
-  return b;
-}
+struct XpartWs {      // E >= 1 here (an empty graph is laid out as one edge)
+  CcWs cc;
+  uint8_t* active;
+  u64 *k0, *k1, *ukeys;
+  unsigned *counts, *nruns;
+  void* tmp; size_t tmp_bytes;
+  XpartWs(Carve& w, long n, long E) : cc(w, n) {
+    active = w.take_n<uint8_t>(E);
+    k0 = w.take_n<u64>(E); k1 = w.take_n<u64>(E); ukeys = w.take_n<u64>(E);
+    counts = w.take_n<unsigned>(E + 1);
+    nruns = (unsigned*)w.take(256);
+    tmp_bytes = std::max(radix_sort_keys_bytes<u64>(E, 0, 64), run_length_encode_bytes<u64, unsigned>(E));
+    tmp = w.take(tmp_bytes);
+  }
+};
+
+// per-workgroup partial sums of the forward: [blocks, 2] float64
+struct EdgeForwardWs {
+  double* partials;
+  EdgeForwardWs(Carve& w, long E) { partials = w.take_n<double>((size_t)spg_cdiv(std::max<long>(E, 1), EL_BLOCK) * 2); }
+};
 
 template <int LPV>
 void launch_bwd(const BwdArgs& a, hipStream_t st) {
@@ -469,8 +458,9 @@ bool sizes_ok(long n, long E) { return n >= 1 && E >= 0 && n < INT_MAX && E < IN
 
 extern "C" size_t spg_edgegraph_workspace_bytes(long n, long E) {
   (void)n;
-  if (E < 0) E = 0;
-  return 3 * align256((size_t)(2 * E) * 4) + align256(sort32_tmp(2 * std::max<long>(E, 1))) + 4096;
+  Carve w;
+  EdgeGraphWs l(w, std::max<long>(E, 0));
+  return w.used();
 }
 
 extern "C" int spg_edgegraph_build(const int64_t* src, const int64_t* tgt, long E, long n, int32_t* rowptr, uint32_t* inc, int32_t* ends,
@@ -478,19 +468,19 @@ extern "C" int spg_edgegraph_build(const int64_t* src, const int64_t* tgt, long 
   SPG_CHECK_ARG(rowptr && error_flag && (E == 0 || (src && tgt && inc && ends && workspace)), "bad argument");
   SPG_CHECK_ARG(sizes_ok(n, E), "1 <= n < 2^31 - 1 and 0 <= E < 2^30 (an incidence is edge << 1 | side in 32 bits)");
   hipStream_t st = (hipStream_t)stream;
-  SPG_RP(hipMemsetAsync(error_flag, 0, sizeof(int32_t), st));
   const dim3 block(EL_BLOCK);
   if (E == 0) {
+    SPG_RP(hipMemsetAsync(error_flag, 0, sizeof(int32_t), st));
     SPG_RP(hipMemsetAsync(rowptr, 0, (size_t)(n + 1) * 4, st));
     return 0;
   }
-  Carve w{(char*)workspace, workspace_bytes};
-  unsigned* k0 = (unsigned*)w.take((size_t)(2 * E) * 4);
-  unsigned* k1 = (unsigned*)w.take((size_t)(2 * E) * 4);
-  unsigned* v0 = (unsigned*)w.take((size_t)(2 * E) * 4);
-  size_t tmp_bytes = sort32_tmp(2 * E);
-  void* tmp = w.take(tmp_bytes);
-  SPG_CHECK_ARG(w.ok, "workspace too small (spg_edgegraph_workspace_bytes)");
+  Carve w(workspace, workspace_bytes);
+  EdgeGraphWs l(w, E);
+  unsigned *k0 = l.k0, *k1 = l.k1, *v0 = l.v0;
+  void* tmp = l.tmp;
+  size_t tmp_bytes = l.tmp_bytes;
+  SPG_CHECK_ARG(w.ok, "workspace too small (spg_edgegraph_workspace_bytes)");      // (before anything is written)
+  SPG_RP(hipMemsetAsync(error_flag, 0, sizeof(int32_t), st));
   hipLaunchKernelGGL(eg_keys_kernel, dim3(spg_cdiv(E, EL_BLOCK)), block, 0, st, src, tgt, E, n, k0, v0, (int2*)ends, error_flag);
   SPG_LAUNCH_CHECK();
   SPG_RP(rocprim::radix_sort_pairs(tmp, tmp_bytes, (const unsigned*)k0, k1, (const unsigned*)v0, (unsigned*)inc, (size_t)(2 * E), 0,
@@ -500,7 +490,11 @@ extern "C" int spg_edgegraph_build(const int64_t* src, const int64_t* tgt, long 
   return 0;
 }
 
-extern "C" size_t spg_edge_forward_workspace_bytes(long E) { return align256((size_t)spg_cdiv(std::max<long>(E, 1), EL_BLOCK) * 16) + 256; }
+extern "C" size_t spg_edge_forward_workspace_bytes(long E) {
+  Carve w;
+  EdgeForwardWs l(w, E);
+  return w.used();
+}
 
 extern "C" int spg_edge_forward(int mode, const float* emb, long n, int d, const int32_t* ends, long E, int dist_type, int intra, int inter,
                                 const uint8_t* is_transition, const float* weights, float* diff, float* dx, float* dl, double* loss_out,
@@ -509,6 +503,7 @@ extern "C" int spg_edge_forward(int mode, const float* emb, long n, int d, const
   SPG_CHECK_ARG(sizes_ok(n, E), "1 <= n < 2^31 - 1 and 0 <= E < 2^30");
   SPG_CHECK_ARG(dist_type >= DIST_EUCLIDIAN && dist_type <= DIST_SCALAR, "dist_type: 0 euclidian, 1 intrinsic, 2 scalar");
   const bool do_dist = mode & 1, do_loss = mode & 2;
+  double* partials = nullptr;
   if (do_dist) {
     SPG_CHECK_ARG(d >= 1 && d <= 64, "1 <= d <= 64");
     SPG_CHECK_ARG(E == 0 || (emb && ends && diff), "bad argument");
@@ -518,13 +513,15 @@ extern "C" int spg_edge_forward(int mode, const float* emb, long n, int d, const
   if (do_loss) {
     SPG_CHECK_ARG(intra >= INTRA_TV && intra <= INTRA_TVH && inter >= INTER_ZHANG && inter <= INTER_TVMINUS, "intra: 0 tv, 1 laplacian, 2 TVH; inter: 0 zhang, 1 TVminus");
     SPG_CHECK_ARG(loss_out && workspace && (E == 0 || (is_transition && weights && diff && dl)), "bad argument");
-    SPG_CHECK_ARG(workspace_bytes >= spg_edge_forward_workspace_bytes(E), "workspace too small (spg_edge_forward_workspace_bytes)");
+    Carve w(workspace, workspace_bytes);
+    partials = EdgeForwardWs(w, E).partials;
+    SPG_CHECK_ARG(w.ok, "workspace too small (spg_edge_forward_workspace_bytes)");
   }
   hipStream_t st = (hipStream_t)stream;
   FwdArgs a{};
   a.emb = emb; a.ends = (const int2*)ends; a.trans = is_transition; a.weights = weights; a.diff = diff;
   a.dx = dist_type == DIST_INTRINSIC ? dx : nullptr;
-  a.dl = dl; a.partials = (double*)workspace; a.E = E; a.d = d; a.dist_type = dist_type; a.intra = intra; a.inter = inter;
+  a.dl = dl; a.partials = partials; a.E = E; a.d = d; a.dist_type = dist_type; a.intra = intra; a.inter = inter;
   const int nb = spg_cdiv(E, EL_BLOCK);
   if (nb > 0) {
 #define EL_FWD(DT)                                                                                                 \
@@ -540,7 +537,7 @@ extern "C" int spg_edge_forward(int mode, const float* emb, long n, int d, const
     SPG_LAUNCH_CHECK();
   }
   if (do_loss) {
-    hipLaunchKernelGGL(edge_loss_final_kernel, dim3(1), dim3(EL_BLOCK), 0, st, (const double*)workspace, (long)nb, loss_out);
+    hipLaunchKernelGGL(edge_loss_final_kernel, dim3(1), dim3(EL_BLOCK), 0, st, (const double*)partials, (long)nb, loss_out);
     SPG_LAUNCH_CHECK();
   }
   return 0;
@@ -580,19 +577,26 @@ extern "C" int spg_edge_backward(const float* emb, long n, int d, const int32_t*
   return 0;
 }
 
-extern "C" size_t spg_cc_workspace_bytes(long n) { return cc_bytes(std::max<long>(n, 1)) + 4096; }
+extern "C" size_t spg_cc_workspace_bytes(long n) {
+  Carve w;
+  CcWs l(w, std::max<long>(n, 1));
+  return w.used();
+}
 
 extern "C" int spg_connected_components(const int32_t* ends, const uint8_t* active, long E, long n, int32_t* in_component,
                                         int32_t* component_size, int32_t* n_components, void* workspace, size_t workspace_bytes, void* stream) {
   SPG_CHECK_ARG(sizes_ok(n, E), "1 <= n < 2^31 - 1 and 0 <= E < 2^30");
   SPG_CHECK_ARG(in_component && component_size && n_components && workspace && (E == 0 || (ends && active)), "bad argument");
-  return cc_run((const int2*)ends, active, E, n, in_component, component_size, n_components, workspace, workspace_bytes, (hipStream_t)stream);
+  Carve w(workspace, workspace_bytes);
+  CcWs l(w, n);
+  SPG_CHECK_ARG(w.ok, "workspace too small (spg_cc_workspace_bytes)");
+  return cc_run((const int2*)ends, active, E, n, in_component, component_size, n_components, l, (hipStream_t)stream);
 }
 
 extern "C" size_t spg_xpart_workspace_bytes(long n, long E) {
-  n = std::max<long>(n, 1); E = std::max<long>(E, 1);
-  return cc_bytes(n) + align256((size_t)E) + 3 * align256((size_t)E * 8) + align256((size_t)(E + 1) * 4) + align256(256) +
-         align256(max2(sort64_tmp(E), rle_tmp(E))) + 4096;
+  Carve w;
+  XpartWs l(w, std::max<long>(n, 1), std::max<long>(E, 1));
+  return w.used();
 }
 
 extern "C" int spg_xpart_weights(const int32_t* ends, long E, long n, const int32_t* pred_in_component, const uint8_t* is_transition,
@@ -602,23 +606,20 @@ extern "C" int spg_xpart_weights(const int32_t* ends, long E, long n, const int3
   SPG_CHECK_ARG(pred_in_component && in_component && component_size && n_components && workspace && (E == 0 || (ends && is_transition && weights)),
                 "bad argument");
   hipStream_t st = (hipStream_t)stream;
-  Carve w{(char*)workspace, workspace_bytes};
-  void* ccws = w.take(cc_bytes(n));
-  uint8_t* active = (uint8_t*)w.take((size_t)std::max<long>(E, 1));
-  u64* k0 = (u64*)w.take((size_t)std::max<long>(E, 1) * 8);
-  u64* k1 = (u64*)w.take((size_t)std::max<long>(E, 1) * 8);
-  u64* ukeys = (u64*)w.take((size_t)std::max<long>(E, 1) * 8);
-  unsigned* counts = (unsigned*)w.take((size_t)(std::max<long>(E, 1) + 1) * 4);
-  unsigned* nruns = (unsigned*)w.take(256);
-  size_t tmp_bytes = max2(sort64_tmp(std::max<long>(E, 1)), rle_tmp(std::max<long>(E, 1)));
-  void* tmp = w.take(tmp_bytes);
+  Carve w(workspace, workspace_bytes);
+  XpartWs l(w, n, std::max<long>(E, 1));
+  uint8_t* active = l.active;
+  u64 *k0 = l.k0, *k1 = l.k1, *ukeys = l.ukeys;
+  unsigned *counts = l.counts, *nruns = l.nruns;
+  void* tmp = l.tmp;
+  const size_t tmp_bytes = l.tmp_bytes;
   SPG_CHECK_ARG(w.ok, "workspace too small (spg_xpart_workspace_bytes)");
   const dim3 block(EL_BLOCK), ge(spg_cdiv(std::max<long>(E, 1), EL_BLOCK));
   if (E > 0) {
     hipLaunchKernelGGL(xp_active_kernel, ge, block, 0, st, (const int2*)ends, pred_in_component, is_transition, E, active);
     SPG_LAUNCH_CHECK();
   }
-  SPG_TRY(cc_run((const int2*)ends, active, E, n, in_component, component_size, n_components, ccws, cc_bytes(n), st));
+  SPG_TRY(cc_run((const int2*)ends, active, E, n, in_component, component_size, n_components, l.cc, st));
   if (E == 0) return 0;
   hipLaunchKernelGGL(xp_keys_kernel, ge, block, 0, st, (const int2*)ends, (const int32_t*)in_component, is_transition, E, k0);
   SPG_LAUNCH_CHECK();

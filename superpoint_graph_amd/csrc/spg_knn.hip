@@ -28,45 +28,17 @@
 #include <cfloat>
 #include <climits>
 #include <cstring>
-#include <rocprim/rocprim.hpp>
 
 #include "../../include/spg_hip.h"
-#include "spg_common.h"
+#include "spg_part.h"
 
 namespace {
-
-typedef unsigned long long u64;
-
-#define SPG_RP(expr)                                                                      \
-  do {                                                                                    \
-    hipError_t e__ = (expr);                                                              \
-    if (e__ != hipSuccess) {                                                              \
-      spg_set_error("%s:%d: %s: %s", __FILE__, __LINE__, #expr, hipGetErrorString(e__));  \
-      return (int)e__;                                                                    \
-    }                                                                                     \
-  } while (0)
 
 constexpr int KNN_BITS = 21;                     // fine cells per axis: 2^21 (3 x 21 = 63-bit Morton keys)
 constexpr int KNN_TARGET = 32;                   // aimed-at mean points per occupied cell
 constexpr long KNN_QCHUNK = 1L << 22;            // queries per internal chunk (query-set mode)
 constexpr int KNN_MAX_K = 47;                    // k + 1 <= 48: the largest register-resident list without scratch
 constexpr int KNN_BLOCK = 256;
-
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-inline size_t max2(size_t a, size_t b) { return a > b ? a : b; }
-
-struct Carve {
-  char* p;
-  size_t left;
-  bool ok = true;
-  void* take(size_t bytes) {
-    bytes = align256(bytes);
-    if (bytes > left) { ok = false; return nullptr; }
-    void* r = p;
-    p += bytes; left -= bytes;
-    return r;
-  }
-};
 
 // written by the device during the build; lives at the start of the workspace
 struct KnnParams {
@@ -85,13 +57,6 @@ struct KnnParams {
   double slack;          // bound on |true position - cell box| from the float32 cell assignment and float64 rounding
   long n;                // points
 };
-
-__device__ __forceinline__ unsigned ordered_bits(float f) {
-  unsigned b = __float_as_uint(f);
-  if (b == 0x80000000u) b = 0u;
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float from_ordered(unsigned b) { return __uint_as_float((b & 0x80000000u) ? (b & 0x7fffffffu) : ~b); }
 
 __device__ __forceinline__ u64 spread3(unsigned v) {
   u64 x = v & 0x1fffffu;
@@ -450,66 +415,38 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_query_kernel(QueryArgs a) {
   }
 }
 
-// ---- rocPRIM scratch sizes ----
-size_t sort_tmp(long n) {
-  size_t b = 0;
-  (void)rocprim::radix_sort_pairs(nullptr, b, (u64*)nullptr, (u64*)nullptr, (unsigned*)nullptr, (unsigned*)nullptr, (size_t)n, 0, 63, (hipStream_t)0);
-  return b;
-}
-size_t rle_tmp(long n) {
-  size_t b = 0;
-  (void)rocprim::run_length_encode(nullptr, b, (u64*)nullptr, (unsigned)n, (u64*)nullptr, (unsigned*)nullptr, (unsigned*)nullptr, (hipStream_t)0);
-  return b;
-}
-size_t scan_tmp(long n) {
-  size_t b = 0;
-  (void)rocprim::exclusive_scan(nullptr, b, (unsigned*)nullptr, (unsigned*)nullptr, 0u, (size_t)n, rocprim::plus<unsigned>(), (hipStream_t)0);
-  return b;
-}
-size_t seg_tmp(long n) { return max2(max2(sort_tmp(n), rle_tmp(n)), scan_tmp(n + 1)); }
-
-// sort + run-length scratch for m keys (the build and every query chunk use the same shape)
+// sort + run-length buffers for m keys (the build and every query chunk use the same shape; only a query chunk keeps its cells)
 struct SegWs {
   u64 *k0, *k1, *ukeys;
   unsigned *i0, *i1, *counts, *start;
   void* tmp; size_t tmp_bytes;
+  SegWs(Carve& w, long m, bool with_cells) {
+    k0 = w.take_n<u64>(m); k1 = w.take_n<u64>(m);
+    ukeys = with_cells ? w.take_n<u64>(m) : nullptr;
+    i0 = w.take_n<unsigned>(m); i1 = w.take_n<unsigned>(m);
+    counts = w.take_n<unsigned>(m + 1);
+    start = with_cells ? w.take_n<unsigned>(m + 1) : nullptr;
+    tmp_bytes = std::max({radix_sort_pairs_bytes<u64, unsigned>(m, 0, 63), run_length_encode_bytes<u64, unsigned>(m),
+                          exclusive_scan_bytes<unsigned>(m + 1)});
+    tmp = w.take(tmp_bytes);
+  }
 };
-size_t seg_bytes(long m) {
-  return 3 * align256((size_t)m * 8) + 2 * align256((size_t)m * 4) + 2 * align256((size_t)(m + 1) * 4) + align256(seg_tmp(m));
-}
-SegWs seg_carve(Carve& w, long m, bool with_cells) {
-  SegWs s;
-  s.k0 = (u64*)w.take((size_t)m * 8); s.k1 = (u64*)w.take((size_t)m * 8);
-  s.ukeys = with_cells ? (u64*)w.take((size_t)m * 8) : nullptr;
-  s.i0 = (unsigned*)w.take((size_t)m * 4); s.i1 = (unsigned*)w.take((size_t)m * 4);
-  s.counts = (unsigned*)w.take((size_t)(m + 1) * 4);
-  s.start = with_cells ? (unsigned*)w.take((size_t)(m + 1) * 4) : nullptr;
-  s.tmp_bytes = seg_tmp(m);
-  s.tmp = w.take(s.tmp_bytes);
-  return s;
-}
+size_t seg_bytes(long m, bool with_cells) { Carve w; SegWs s(w, m, with_cells); return w.used(); }
 
-// persistent part: parameters, points in cell order, occupied cells and their starts
+// persistent part: parameters, points in cell order, occupied cells and their starts; the build and the query chunks carve the rest
 struct KnnWs {
   KnnParams* prm;
   float4* pts;
   u64* ukeys;
   unsigned* ustart;
-  char* scratch; size_t scratch_bytes;
-  bool ok;
+  KnnWs(Carve& w, long n) {
+    prm = w.take_n<KnnParams>(1);
+    pts = w.take_n<float4>(n);
+    ukeys = w.take_n<u64>(n);
+    ustart = w.take_n<unsigned>(n + 1);
+  }
 };
-size_t persistent_bytes(long n) { return align256(sizeof(KnnParams)) + align256((size_t)n * 16) + align256((size_t)n * 8) + align256((size_t)(n + 1) * 4); }
-KnnWs knn_carve(void* ws, size_t bytes, long n) {
-  Carve w{(char*)ws, bytes};
-  KnnWs k;
-  k.prm = (KnnParams*)w.take(sizeof(KnnParams));
-  k.pts = (float4*)w.take((size_t)n * 16);
-  k.ukeys = (u64*)w.take((size_t)n * 8);
-  k.ustart = (unsigned*)w.take((size_t)(n + 1) * 4);
-  k.ok = w.ok;
-  k.scratch = w.p; k.scratch_bytes = w.left;
-  return k;
-}
+size_t persistent_bytes(long n) { Carve w; KnnWs k(w, n); return w.used(); }
 
 __global__ void error_out_kernel(const KnnParams* __restrict__ p, int32_t* __restrict__ out) { *out = (int32_t)(p->flag | p->qflag); }
 
@@ -517,8 +454,8 @@ __global__ void error_out_kernel(const KnnParams* __restrict__ p, int32_t* __res
 // leaves after the persistent part; 0 when not even 64 queries fit
 long query_chunk(size_t scratch_bytes, long n_query) {
   long m = std::min(n_query, KNN_QCHUNK);
-  while (m > 64 && seg_bytes(m) + 4096 > scratch_bytes) m = (m + 1) / 2;
-  return seg_bytes(m) + 4096 <= scratch_bytes ? m : 0;
+  while (m > 64 && seg_bytes(m, true) > scratch_bytes) m = (m + 1) / 2;
+  return seg_bytes(m, true) <= scratch_bytes ? m : 0;
 }
 
 int launch_query(const QueryArgs& a, long max_groups, hipStream_t st) {
@@ -544,8 +481,8 @@ extern "C" size_t spg_knn_workspace_bytes(long n_ref, long n_query, int k) {
   (void)k;
   if (n_ref < 1) n_ref = 1;
   if (n_query < 0) n_query = 0;
-  const long m = std::min(n_query, KNN_QCHUNK);
-  return persistent_bytes(n_ref) + max2(seg_bytes(n_ref), m > 0 ? seg_bytes(m) : 0) + 4096;
+  const long m = std::min(n_query, KNN_QCHUNK);      // the larger of the build layout and the layout of a full query chunk
+  return persistent_bytes(n_ref) + std::max(seg_bytes(n_ref, false), m > 0 ? seg_bytes(m, true) : 0);
 }
 
 extern "C" int spg_knn_build(const float* ref_xyz, long n_ref, float cell_size, int32_t* error_flag, void* workspace,
@@ -554,10 +491,10 @@ extern "C" int spg_knn_build(const float* ref_xyz, long n_ref, float cell_size, 
   SPG_CHECK_ARG(n_ref < (1L << 32) - 1, "more than 2^32 - 2 reference points (indices are uint32)");
   SPG_CHECK_ARG(!(cell_size < 0.f) && !(cell_size > FLT_MAX), "cell_size must be >= 0 and finite (0 = automatic)");
   hipStream_t st = (hipStream_t)stream;
-  KnnWs k = knn_carve(workspace, workspace_bytes, n_ref);
-  Carve w{k.scratch, k.scratch_bytes};
-  SegWs s = seg_carve(w, n_ref, false);
-  SPG_CHECK_ARG(k.ok && w.ok, "workspace too small (spg_knn_workspace_bytes)");
+  Carve w(workspace, workspace_bytes);
+  KnnWs k(w, n_ref);
+  SegWs s(w, n_ref, false);
+  SPG_CHECK_ARG(w.ok, "workspace too small (spg_knn_workspace_bytes)");
   const long n = n_ref;
   const dim3 block(256), grid(spg_cdiv(n, 256));
   SPG_RP(hipMemsetAsync(k.prm, 0, sizeof(KnnParams), st));
@@ -598,8 +535,9 @@ extern "C" int spg_knn_query(const float* query_xyz, long n_query, long n_ref, i
   SPG_CHECK_ARG(self_query ? (n_query == n_ref && k < n_ref) : (n_query >= 0 && n_query < (1L << 32) - 1 && k <= n_ref && (n_query == 0 || query_xyz)),
                 "self query: n_query == n_ref > k; query set: k <= n_ref");
   hipStream_t st = (hipStream_t)stream;
-  KnnWs w = knn_carve(workspace, workspace_bytes, n_ref);
-  SPG_CHECK_ARG(w.ok, "workspace too small (spg_knn_workspace_bytes)");
+  Carve c(workspace, workspace_bytes);
+  KnnWs w(c, n_ref);
+  SPG_CHECK_ARG(c.ok, "workspace too small (spg_knn_workspace_bytes)");
   SPG_RP(hipMemsetAsync(&w.prm->qflag, 0, sizeof(unsigned), st));
   QueryArgs a{};
   a.pts = w.pts; a.ukeys = w.ukeys; a.ustart = w.ustart; a.prm = w.prm;
@@ -608,10 +546,9 @@ extern "C" int spg_knn_query(const float* query_xyz, long n_query, long n_ref, i
     a.seg_keys = w.ukeys; a.seg_start = w.ustart; a.nseg = &w.prm->n_cells;
     SPG_TRY(launch_query(a, n_ref, st));
   } else if (n_query > 0) {
-    const long m = query_chunk(w.scratch_bytes, n_query);
+    const long m = query_chunk(c.left(), n_query);
     SPG_CHECK_ARG(m > 0, "workspace too small for a query chunk (spg_knn_workspace_bytes)");
-    Carve c{w.scratch, w.scratch_bytes};
-    SegWs s = seg_carve(c, m, true);
+    SegWs s(c, m, true);
     SPG_CHECK_ARG(c.ok, "workspace too small for a query chunk (spg_knn_workspace_bytes)");
     a.qxyz = query_xyz; a.qidx = s.i1; a.seg_keys = s.ukeys; a.seg_start = s.start; a.nseg = &w.prm->n_qseg;
     for (long q0 = 0; q0 < n_query; q0 += m) {

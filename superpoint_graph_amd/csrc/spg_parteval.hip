@@ -25,46 +25,17 @@
 //   scalar unit, block sum, one 64-bit atomic per cell and block.
 #include <climits>
 #include <cstring>
-#include <rocprim/rocprim.hpp>
 
 #include "../../include/spg_hip.h"
-#include "spg_common.h"
+#include "spg_part.h"
 
 namespace {
-
-typedef unsigned long long u64;
-
-#define SPG_RP(expr)                                                                      \
-  do {                                                                                    \
-    hipError_t e__ = (expr);                                                              \
-    if (e__ != hipSuccess) {                                                              \
-      spg_set_error("%s:%d: %s: %s", __FILE__, __LINE__, #expr, hipGetErrorString(e__));  \
-      return (int)e__;                                                                    \
-    }                                                                                     \
-  } while (0)
 
 constexpr int PE_BLOCK = 256;
 constexpr int CL_ROWS = 32;            // rows of the component order one lane group sums before it has to flush
 constexpr int PE_MAX_CLASSES = 64;
 constexpr int BC_MAX_BLOCKS = 2048;    // grid of the boundary counts (grid-stride): 4 atomics per block
 enum { PE_ERR_COMPONENT = 1, PE_ERR_VALUE = 2 };
-
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-inline size_t max2(size_t a, size_t b) { return a > b ? a : b; }
-inline int bits_of(unsigned long v) { int b = 1; while (b < 64 && (v >> b) != 0) ++b; return b; }
-
-struct Carve {
-  char* p;
-  size_t left;
-  bool ok = true;
-  void* take(size_t bytes) {
-    bytes = align256(bytes);
-    if (bytes > left) { ok = false; return nullptr; }
-    void* r = p;
-    p += bytes; left -= bytes;
-    return r;
-  }
-};
 
 bool sizes_ok(long n, long n_com) { return n >= 1 && n < INT_MAX && n_com >= 1 && n_com < INT_MAX; }
 
@@ -101,11 +72,15 @@ __global__ void pi_offsets_kernel(const unsigned* __restrict__ keys, long n, lon
   if (c < n_com) size[c] = (int32_t)(pe_lower_bound(keys, lo, n, (unsigned)c + 1u) - lo);
 }
 
-size_t sort32_tmp(long m) {
-  size_t b = 0;
-  (void)rocprim::radix_sort_pairs(nullptr, b, (unsigned*)nullptr, (unsigned*)nullptr, (unsigned*)nullptr, (unsigned*)nullptr, (size_t)m, 0, 32, (hipStream_t)0);
-  return b;
-}
+struct PartitionIndexWs {      // (component, vertex) pairs: keys in / out, values in; rocPRIM scratch
+  unsigned *k0, *k1, *v0;
+  void* tmp; size_t tmp_bytes;
+  PartitionIndexWs(Carve& w, long n) {
+    k0 = w.take_n<unsigned>(n); k1 = w.take_n<unsigned>(n); v0 = w.take_n<unsigned>(n);
+    tmp_bytes = radix_sort_pairs_bytes<unsigned, unsigned>(n, 0, 32);
+    tmp = w.take(tmp_bytes);
+  }
+};
 
 // -------------------------------------------------------------------------------------------------------------------
 // label sums, majority label, confusion matrix
@@ -214,16 +189,19 @@ __global__ void cm_final_kernel(const u64* __restrict__ best, long n_com, int32_
   value[c] = b == 0 ? -1 : (int32_t)(0x7FFFFFFFu - (unsigned)(b & 0xFFFFFFFFu));
 }
 
-size_t sort64_tmp(long m) {
-  size_t b = 0;
-  (void)rocprim::radix_sort_keys(nullptr, b, (u64*)nullptr, (u64*)nullptr, (size_t)m, 0, 64, (hipStream_t)0);
-  return b;
-}
-size_t rle_tmp(long m) {
-  size_t b = 0;
-  (void)rocprim::run_length_encode(nullptr, b, (u64*)nullptr, (unsigned)m, (u64*)nullptr, (unsigned*)nullptr, (unsigned*)nullptr, (hipStream_t)0);
-  return b;
-}
+struct ComponentModeWs {
+  u64 *k0, *k1, *ukeys, *best;
+  unsigned *counts, *nruns;
+  void* tmp; size_t tmp_bytes;
+  ComponentModeWs(Carve& w, long n, long n_com) {
+    k0 = w.take_n<u64>(n); k1 = w.take_n<u64>(n); ukeys = w.take_n<u64>(n);
+    counts = w.take_n<unsigned>(n + 1);
+    nruns = (unsigned*)w.take(256);
+    best = w.take_n<u64>(n_com);
+    tmp_bytes = std::max(radix_sort_keys_bytes<u64>(n, 0, 64), run_length_encode_bytes<u64, unsigned>(n));
+    tmp = w.take(tmp_bytes);
+  }
+};
 
 // -------------------------------------------------------------------------------------------------------------------
 // SEAL weights
@@ -329,6 +307,15 @@ __global__ __launch_bounds__(PE_BLOCK) void bc_counts_kernel(const uint8_t* __re
   }
 }
 
+struct RelaxEdgesWs {      // byte marks per vertex, flag word
+  uint8_t* marks;
+  unsigned* flags;
+  RelaxEdgesWs(Carve& w, long n) {
+    marks = w.take_n<uint8_t>(n);
+    flags = (unsigned*)w.take(256);
+  }
+};
+
 template <int LPR>
 void launch_labels(const uint32_t* labels, const int32_t* in_component, const int32_t* order, long n, int C, long n_com, u64* sums,
                    int32_t* label_com, u64* confusion, hipStream_t st) {
@@ -343,8 +330,9 @@ void launch_labels(const uint32_t* labels, const int32_t* in_component, const in
 
 extern "C" size_t spg_partition_index_workspace_bytes(long n, long n_com) {
   (void)n_com;
-  n = std::max<long>(n, 1);
-  return 3 * align256((size_t)n * 4) + align256(sort32_tmp(n)) + 4096;
+  Carve w;
+  PartitionIndexWs l(w, std::max<long>(n, 1));
+  return w.used();
 }
 
 extern "C" int spg_partition_index(const int32_t* in_component, long n, long n_com, int32_t* order, int32_t* offsets, int32_t* size,
@@ -352,12 +340,11 @@ extern "C" int spg_partition_index(const int32_t* in_component, long n, long n_c
   SPG_CHECK_ARG(sizes_ok(n, n_com), "1 <= n < 2^31 - 1 and 1 <= n_com < 2^31 - 1");
   SPG_CHECK_ARG(in_component && order && offsets && size && error_flag && workspace, "bad argument");
   hipStream_t st = (hipStream_t)stream;
-  Carve w{(char*)workspace, workspace_bytes};
-  unsigned* k0 = (unsigned*)w.take((size_t)n * 4);
-  unsigned* k1 = (unsigned*)w.take((size_t)n * 4);
-  unsigned* v0 = (unsigned*)w.take((size_t)n * 4);
-  size_t tmp_bytes = sort32_tmp(n);
-  void* tmp = w.take(tmp_bytes);
+  Carve w(workspace, workspace_bytes);
+  PartitionIndexWs l(w, n);
+  unsigned *k0 = l.k0, *k1 = l.k1, *v0 = l.v0;
+  void* tmp = l.tmp;
+  size_t tmp_bytes = l.tmp_bytes;
   SPG_CHECK_ARG(w.ok, "workspace too small (spg_partition_index_workspace_bytes)");
   const dim3 block(PE_BLOCK);
   hipLaunchKernelGGL(pi_keys_kernel, dim3(spg_cdiv(n, PE_BLOCK)), block, 0, st, in_component, n, n_com, k0, v0, error_flag);
@@ -395,9 +382,9 @@ extern "C" int spg_component_label_majority(const uint32_t* labels, long n, int 
 }
 
 extern "C" size_t spg_component_mode_workspace_bytes(long n, long n_com) {
-  n = std::max<long>(n, 1); n_com = std::max<long>(n_com, 1);
-  return 3 * align256((size_t)n * 8) + align256((size_t)(n + 1) * 4) + align256(256) + align256((size_t)n_com * 8) +
-         align256(max2(sort64_tmp(n), rle_tmp(n))) + 4096;
+  Carve w;
+  ComponentModeWs l(w, std::max<long>(n, 1), std::max<long>(n_com, 1));
+  return w.used();
 }
 
 extern "C" int spg_component_mode(const int32_t* in_component, const int32_t* values, long n, long n_com, int32_t* freq, int32_t* value,
@@ -405,15 +392,12 @@ extern "C" int spg_component_mode(const int32_t* in_component, const int32_t* va
   SPG_CHECK_ARG(sizes_ok(n, n_com), "1 <= n < 2^31 - 1 and 1 <= n_com < 2^31 - 1");
   SPG_CHECK_ARG(in_component && values && freq && value && error_flag && workspace, "bad argument");
   hipStream_t st = (hipStream_t)stream;
-  Carve w{(char*)workspace, workspace_bytes};
-  u64* k0 = (u64*)w.take((size_t)n * 8);
-  u64* k1 = (u64*)w.take((size_t)n * 8);
-  u64* ukeys = (u64*)w.take((size_t)n * 8);
-  unsigned* counts = (unsigned*)w.take((size_t)(n + 1) * 4);
-  unsigned* nruns = (unsigned*)w.take(256);
-  u64* best = (u64*)w.take((size_t)n_com * 8);
-  size_t tmp_bytes = max2(sort64_tmp(n), rle_tmp(n));
-  void* tmp = w.take(tmp_bytes);
+  Carve w(workspace, workspace_bytes);
+  ComponentModeWs l(w, n, n_com);
+  u64 *k0 = l.k0, *k1 = l.k1, *ukeys = l.ukeys, *best = l.best;
+  unsigned *counts = l.counts, *nruns = l.nruns;
+  void* tmp = l.tmp;
+  const size_t tmp_bytes = l.tmp_bytes;
   SPG_CHECK_ARG(w.ok, "workspace too small (spg_component_mode_workspace_bytes)");
   const dim3 block(PE_BLOCK), gv(spg_cdiv(n, PE_BLOCK));
   SPG_RP(hipMemsetAsync(best, 0, (size_t)n_com * 8, st));
@@ -442,7 +426,11 @@ extern "C" int spg_seal_weights(const int32_t* ends, long E, long n, const int32
   return 0;
 }
 
-extern "C" size_t spg_relax_edges_workspace_bytes(long n) { return align256((size_t)std::max<long>(n, 1)) + align256(256) + 4096; }
+extern "C" size_t spg_relax_edges_workspace_bytes(long n) {
+  Carve w;
+  RelaxEdgesWs l(w, std::max<long>(n, 1));
+  return w.used();
+}
 
 extern "C" int spg_relax_edges(const int32_t* ends, long E, long n, const uint8_t* binary, int tolerance, int mode, uint8_t* relaxed,
                                void* workspace, size_t workspace_bytes, void* stream) {
@@ -453,9 +441,10 @@ extern "C" int spg_relax_edges(const int32_t* ends, long E, long n, const uint8_
   SPG_CHECK_ARG(workspace && (E == 0 || (ends && binary && relaxed)), "bad argument");
   if (E == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  Carve w{(char*)workspace, workspace_bytes};
-  uint8_t* marks = (uint8_t*)w.take((size_t)n);
-  unsigned* flags = (unsigned*)w.take(256);
+  Carve w(workspace, workspace_bytes);
+  RelaxEdgesWs l(w, n);
+  uint8_t* marks = l.marks;
+  unsigned* flags = l.flags;
   SPG_CHECK_ARG(w.ok, "workspace too small (spg_relax_edges_workspace_bytes)");
   SPG_RP(hipMemcpyAsync(relaxed, binary, (size_t)E, hipMemcpyDeviceToDevice, st));
   if (tolerance == 0) return 0;

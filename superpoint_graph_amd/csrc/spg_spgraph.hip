@@ -21,52 +21,11 @@
 // accumulated in float64 and rounded once (the reference accumulates in float32: tolerances in tests/test_gpu_spgraph.py).
 // HBM-bound integer / byte work; nothing here is shaped into a GEMM.
 #include <cstring>
-#include <rocprim/rocprim.hpp>
 
 #include "../../include/spg_hip.h"
-#include "spg_common.h"
+#include "spg_part.h"
 
 namespace {
-
-typedef unsigned long long u64;
-
-#define SPG_RP(expr)                                                                      \
-  do {                                                                                    \
-    hipError_t e__ = (expr);                                                              \
-    if (e__ != hipSuccess) {                                                              \
-      spg_set_error("%s:%d: %s: %s", __FILE__, __LINE__, #expr, hipGetErrorString(e__));  \
-      return (int)e__;                                                                    \
-    }                                                                                     \
-  } while (0)
-
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// ---- float -> unsigned with the same order; -0.0 and +0.0 are one value (np.unique compares with ==) ----
-__device__ __forceinline__ unsigned ordered_bits(float f) {
-  unsigned b = __float_as_uint(f);
-  if (b == 0x80000000u) b = 0u;
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-// correctly rounded float32 square root, as np.sqrt of a float32 array returns it.  (__fsqrt_rn is NOT that here: without
-// OCML_BASIC_ROUNDED_OPERATIONS the HIP headers map it to the native instruction, good to one ulp.)  The float64 root is correctly
-// rounded and 53 >= 2 * 24 + 2 bits, so rounding it once more to float32 cannot differ from rounding the exact root.
-__device__ __forceinline__ float sqrt_rn_f32(float x) { return (float)sqrt((double)x); }
-
-// dx*dx + dy*dy (+ dz*dz) in float32, every product and every sum rounded on its own, added left to right -- what numpy does
-// with a float32 array.  (__fmul_rn / __fadd_rn do NOT guarantee that here: without OCML_BASIC_ROUNDED_OPERATIONS the HIP headers
-// define them as plain * and +, which the compiler contracts into fused multiply-adds.)
-__device__ __forceinline__ float sumsq2_rn_f32(float dx, float dy) {
-#pragma clang fp contract(off)
-  const float xx = dx * dx, yy = dy * dy;
-  return xx + yy;
-}
-__device__ __forceinline__ float sumsq3_rn_f32(float dx, float dy, float dz) {
-#pragma clang fp contract(off)
-  const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
-  const float xy = xx + yy;
-  return xy + zz;
-}
 
 // -------------------------------------------------------------------------------------------------------------------
 // interface edges of the tetrahedra (graphs.py:85-107)
@@ -429,50 +388,42 @@ __global__ __launch_bounds__(256) void geof_kernel(const float* __restrict__ xyz
   geof[4 * i + 3] = (float)(u[2] / norm);         // verticality (:447)
 }
 
-struct Carve {
-  char* p;
-  size_t left;
-  bool ok = true;
-  void* take(size_t bytes) {
-    bytes = align256(bytes);
-    if (bytes > left) { ok = false; return nullptr; }
-    void* r = p;
-    p += bytes; left -= bytes;
-    return r;
+// ---- workspace layouts of the three spg_spg_* stages (spg_spg_workspace_bytes(which, n)) ----
+struct UniqueEdgesWs {      // which = 0: sorted keys, keep flags, rocPRIM scratch
+  u64* sorted;
+  unsigned char* flags;
+  void* tmp; size_t tmp_bytes;
+  UniqueEdgesWs(Carve& w, long n) {
+    sorted = w.take_n<u64>(n);
+    flags = w.take_n<unsigned char>(n);
+    tmp_bytes = std::max(radix_sort_keys_bytes<u64>(n, 0, 64), select_bytes<u64, unsigned char>(n));
+    tmp = w.take(tmp_bytes);
   }
 };
-
-size_t sort_keys_tmp(long n) {
-  size_t b = 0;
-  (void)rocprim::radix_sort_keys(nullptr, b, (u64*)nullptr, (u64*)nullptr, (size_t)n, 0, 64, (hipStream_t)0);
-  return b;
-}
-size_t sort_pairs_u64_tmp(long n) {
-  size_t b = 0;
-  (void)rocprim::radix_sort_pairs(nullptr, b, (u64*)nullptr, (u64*)nullptr, (u64*)nullptr, (u64*)nullptr, (size_t)n, 0, 64, (hipStream_t)0);
-  return b;
-}
-size_t sort_pairs_u32_tmp(long n) {
-  size_t b = 0;
-  (void)rocprim::radix_sort_pairs(nullptr, b, (u64*)nullptr, (u64*)nullptr, (unsigned*)nullptr, (unsigned*)nullptr, (size_t)n, 0, 64, (hipStream_t)0);
-  return b;
-}
-size_t select_tmp(long n) {
-  size_t b = 0;
-  (void)rocprim::select(nullptr, b, (u64*)nullptr, (unsigned char*)nullptr, (u64*)nullptr, (u64*)nullptr, (size_t)n, (hipStream_t)0);
-  return b;
-}
-size_t rle_tmp(long n) {
-  size_t b = 0;
-  (void)rocprim::run_length_encode(nullptr, b, (u64*)nullptr, (unsigned)n, (u64*)nullptr, (int64_t*)nullptr, (unsigned*)nullptr, (hipStream_t)0);
-  return b;
-}
-size_t scan_tmp(long n) {
-  size_t b = 0;
-  (void)rocprim::exclusive_scan(nullptr, b, (int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), (hipStream_t)0);
-  return b;
-}
-size_t max2(size_t a, size_t b) { return a > b ? a : b; }
+struct GroupEdgesWs {       // which = 1: run lengths, run count, rocPRIM scratch
+  int64_t* counts;
+  unsigned* nruns;
+  void* tmp; size_t tmp_bytes;
+  GroupEdgesWs(Carve& w, long n) {
+    counts = w.take_n<int64_t>(n + 1);
+    nruns = (unsigned*)w.take(256);
+    tmp_bytes = std::max({radix_sort_pairs_bytes<u64, u64>(n, 0, 64), run_length_encode_bytes<u64, int64_t>(n), exclusive_scan_bytes<int64_t>(n + 1)});
+    tmp = w.take(tmp_bytes);
+  }
+};
+struct SuperpointsWs {      // which = 2: two key arrays, two index arrays, component segments (sized at n_com = n), rocPRIM scratch
+  u64 *k0, *k1;
+  unsigned *i0, *i1;
+  int64_t* offs;
+  void* tmp; size_t tmp_bytes;
+  SuperpointsWs(Carve& w, long n, long n_com) {
+    k0 = w.take_n<u64>(n); k1 = w.take_n<u64>(n);
+    i0 = w.take_n<unsigned>(n); i1 = w.take_n<unsigned>(n);
+    offs = w.take_n<int64_t>(n_com + 1);
+    tmp_bytes = radix_sort_pairs_bytes<u64, unsigned>(n, 0, 64);
+    tmp = w.take(tmp_bytes);
+  }
+};
 
 // -------------------------------------------------------------------------------------------------------------------
 // prune (partition/ply_c/ply_c.cpp:288-382): voxel-grid subsampling -- mean position / mean colour / label and object
@@ -490,7 +441,6 @@ __global__ void minmax_kernel(const float* __restrict__ xyz, long n, unsigned* _
     if ((threadIdx.x & 63) == 0) { atomicMin(&mm[d], ordered_bits(lo[d])); atomicMax(&mm[3 + d], ordered_bits(hi[d])); }
   }
 }
-__device__ __forceinline__ float from_ordered(unsigned b) { return __uint_as_float((b & 0x80000000u) ? (b & 0x7fffffffu) : ~b); }
 
 __global__ void voxel_keys_kernel(const float* __restrict__ xyz, long n, const unsigned* __restrict__ mm, float voxel, u64* __restrict__ keys,
                                   unsigned* __restrict__ idx, unsigned* __restrict__ flag) {
@@ -554,34 +504,23 @@ __global__ void prune_reduce_kernel(const float* __restrict__ xyz, const uint8_t
   o.rgb[3 * r + 2] = (uint8_t)__fdiv_rn((float)cb, count);
 }
 
-size_t prune_rle_tmp(long n) {
-  size_t b = 0;
-  (void)rocprim::run_length_encode(nullptr, b, (u64*)nullptr, (unsigned)n, (u64*)nullptr, (int64_t*)nullptr, (unsigned*)nullptr, (hipStream_t)0);
-  return b;
-}
-
 struct PruneWs {
   unsigned *mm, *nseg, *flag, *idx0, *idx_sorted, *seg_id, *order;
   u64 *keys0, *keys1, *uniq, *first0, *first1;
   int64_t *counts, *seg_off;
   void* tmp; size_t tmp_bytes;
-  bool ok;
+  PruneWs(Carve& w, long n) {
+    mm = (unsigned*)w.take(256); nseg = mm + 8; flag = mm + 9;
+    keys0 = w.take_n<u64>(n); keys1 = w.take_n<u64>(n);
+    idx0 = w.take_n<unsigned>(n); idx_sorted = w.take_n<unsigned>(n);
+    uniq = w.take_n<u64>(n);
+    counts = w.take_n<int64_t>(n + 1); seg_off = w.take_n<int64_t>(n + 1);
+    first0 = w.take_n<u64>(n); first1 = w.take_n<u64>(n);
+    seg_id = w.take_n<unsigned>(n); order = w.take_n<unsigned>(n);
+    tmp_bytes = std::max({radix_sort_pairs_bytes<u64, unsigned>(n, 0, 64), run_length_encode_bytes<u64, int64_t>(n), exclusive_scan_bytes<int64_t>(n + 1)});
+    tmp = w.take(tmp_bytes);
+  }
 };
-PruneWs prune_carve(void* ws, size_t bytes, long n) {
-  Carve w{(char*)ws, bytes};
-  PruneWs p;
-  p.mm = (unsigned*)w.take(256); p.nseg = p.mm + 8; p.flag = p.mm + 9;
-  p.keys0 = (u64*)w.take((size_t)n * 8); p.keys1 = (u64*)w.take((size_t)n * 8);
-  p.idx0 = (unsigned*)w.take((size_t)n * 4); p.idx_sorted = (unsigned*)w.take((size_t)n * 4);
-  p.uniq = (u64*)w.take((size_t)n * 8);
-  p.counts = (int64_t*)w.take((size_t)(n + 1) * 8); p.seg_off = (int64_t*)w.take((size_t)(n + 1) * 8);
-  p.first0 = (u64*)w.take((size_t)n * 8); p.first1 = (u64*)w.take((size_t)n * 8);
-  p.seg_id = (unsigned*)w.take((size_t)n * 4); p.order = (unsigned*)w.take((size_t)n * 4);
-  p.tmp_bytes = max2(max2(sort_pairs_u32_tmp(n), prune_rle_tmp(n)), scan_tmp(n + 1));
-  p.tmp = w.take(p.tmp_bytes);
-  p.ok = w.ok;
-  return p;
-}
 
 }  // namespace
 
@@ -598,16 +537,14 @@ extern "C" int spg_spg_tet_edges(const int32_t* tets, long T, const int32_t* com
 
 extern "C" size_t spg_spg_workspace_bytes(int which, long n) {
   if (n < 1) n = 1;
+  Carve w;
   switch (which) {
-    case 0:   // unique_edges: sorted keys + flags + rocPRIM scratch
-      return align256((size_t)n * 8) + align256((size_t)n) + align256(max2(sort_keys_tmp(n), select_tmp(n))) + 256;
-    case 1:   // group_edges: run lengths + rocPRIM scratch
-      return align256((size_t)(n + 1) * 8) + align256(max2(max2(sort_pairs_u64_tmp(n), rle_tmp(n)), scan_tmp(n + 1))) + 512;
-    case 2:   // superpoints: two key arrays, two index arrays, component segments (n_com <= n), rocPRIM scratch
-      return 2 * align256((size_t)n * 8) + 2 * align256((size_t)n * 4) + align256((size_t)(n + 1) * 8) + align256(sort_pairs_u32_tmp(n)) + 256;
-    default:
-      return 0;
+    case 0: { UniqueEdgesWs l(w, n); break; }
+    case 1: { GroupEdgesWs l(w, n); break; }
+    case 2: { SuperpointsWs l(w, n, n); break; }      // n_com <= n
+    default: break;
   }
+  return w.used();
 }
 
 extern "C" int spg_spg_unique_edges(const uint64_t* keys, long n, const float* xyz, const int32_t* comp, long n_com, float d_max,
@@ -616,11 +553,12 @@ extern "C" int spg_spg_unique_edges(const uint64_t* keys, long n, const float* x
   SPG_CHECK_ARG(n >= 0 && count && (n == 0 || (keys && xyz && comp && edge_keys && cc_keys && workspace)) && n_com > 0, "bad argument");
   hipStream_t st = (hipStream_t)stream;
   if (n == 0) { SPG_RP(hipMemsetAsync(count, 0, sizeof(uint64_t), st)); return 0; }
-  Carve w{(char*)workspace, workspace_bytes};
-  u64* sorted = (u64*)w.take((size_t)n * 8);
-  unsigned char* flags = (unsigned char*)w.take((size_t)n);
-  size_t tb = max2(sort_keys_tmp(n), select_tmp(n));
-  void* tmp = w.take(tb);
+  Carve w(workspace, workspace_bytes);
+  UniqueEdgesWs l(w, n);
+  u64* sorted = l.sorted;
+  unsigned char* flags = l.flags;
+  void* tmp = l.tmp;
+  const size_t tb = l.tmp_bytes;
   SPG_CHECK_ARG(w.ok, "workspace too small (spg_spg_workspace_bytes(0, n))");
   size_t b = tb;
   SPG_RP(rocprim::radix_sort_keys(tmp, b, (const u64*)keys, sorted, (size_t)n, 0, 64, st));
@@ -645,11 +583,12 @@ extern "C" int spg_spg_group_edges(const uint64_t* cc_keys, const uint64_t* edge
     SPG_RP(hipMemsetAsync(seg_off, 0, sizeof(int64_t), st));
     return 0;
   }
-  Carve w{(char*)workspace, workspace_bytes};
-  int64_t* counts = (int64_t*)w.take((size_t)(n + 1) * 8);
-  unsigned* nruns = (unsigned*)w.take(256);
-  size_t tb = max2(max2(sort_pairs_u64_tmp(n), rle_tmp(n)), scan_tmp(n + 1));
-  void* tmp = w.take(tb);
+  Carve w(workspace, workspace_bytes);
+  GroupEdgesWs l(w, n);
+  int64_t* counts = l.counts;
+  unsigned* nruns = l.nruns;
+  void* tmp = l.tmp;
+  const size_t tb = l.tmp_bytes;
   SPG_CHECK_ARG(w.ok, "workspace too small (spg_spg_workspace_bytes(1, n))");
   size_t b = tb;
   SPG_RP(rocprim::radix_sort_pairs(tmp, b, (const u64*)cc_keys, (u64*)cc_sorted, (const u64*)edge_keys, (u64*)edges_sorted, (size_t)n, 0, 64, st));
@@ -671,14 +610,13 @@ extern "C" int spg_spg_superpoints(const float* xyz, long n, const int32_t* comp
                 "bad argument");
   SPG_CHECK_ARG(!(labels && label_rows) && ((labels == nullptr && label_rows == nullptr) || (sp_labels && n_labels >= 0)), "bad label arguments");
   hipStream_t st = (hipStream_t)stream;
-  Carve w{(char*)workspace, workspace_bytes};
-  u64* k0 = (u64*)w.take((size_t)n * 8);
-  u64* k1 = (u64*)w.take((size_t)n * 8);
-  unsigned* i0 = (unsigned*)w.take((size_t)n * 4);
-  unsigned* i1 = (unsigned*)w.take((size_t)n * 4);
-  int64_t* offs = (int64_t*)w.take((size_t)(n_com + 1) * 8);      // component segments of the ordered points
-  size_t tb = sort_pairs_u32_tmp(n);
-  void* tmp = w.take(tb);
+  Carve w(workspace, workspace_bytes);
+  SuperpointsWs l(w, n, n_com);
+  u64 *k0 = l.k0, *k1 = l.k1;
+  unsigned *i0 = l.i0, *i1 = l.i1;
+  int64_t* offs = l.offs;                                          // component segments of the ordered points
+  void* tmp = l.tmp;
+  const size_t tb = l.tmp_bytes;
   SPG_CHECK_ARG(w.ok, "workspace too small (spg_spg_workspace_bytes(2, n))");
   const dim3 grid(spg_cdiv(n, 256)), block(256);
   hipLaunchKernelGGL(point_keys_yz_kernel, grid, block, 0, st, xyz, n, k0, i0);
@@ -731,8 +669,9 @@ extern "C" int spg_compute_geof(const float* xyz, const uint32_t* target, long n
 
 extern "C" size_t spg_prune_workspace_bytes(long n) {
   if (n < 1) n = 1;
-  return 256 + 5 * align256((size_t)n * 8) + 4 * align256((size_t)n * 4) + 2 * align256((size_t)(n + 1) * 8) +
-         align256(max2(max2(sort_pairs_u32_tmp(n), prune_rle_tmp(n)), scan_tmp(n + 1))) + 4096;
+  Carve w;
+  PruneWs p(w, n);
+  return w.used();
 }
 
 // phase 1: voxel of every point, points ordered by voxel, voxels in first-occurrence order; *n_voxels (device int64) for the caller
@@ -740,8 +679,9 @@ extern "C" int spg_prune_voxels(const float* xyz, long n, float voxel_size, int6
                                 size_t workspace_bytes, void* stream) {
   SPG_CHECK_ARG(xyz && n > 0 && n < (1L << 32) && voxel_size > 0.f && n_voxels && workspace, "bad argument");
   hipStream_t st = (hipStream_t)stream;
-  PruneWs p = prune_carve(workspace, workspace_bytes, n);
-  SPG_CHECK_ARG(p.ok, "workspace too small (spg_prune_workspace_bytes(n))");
+  Carve w(workspace, workspace_bytes);
+  PruneWs p(w, n);
+  SPG_CHECK_ARG(w.ok, "workspace too small (spg_prune_workspace_bytes(n))");
   SPG_RP(hipMemsetAsync(p.mm, 0xff, 3 * sizeof(unsigned), st));          // running minima (ordered bits): all ones
   SPG_RP(hipMemsetAsync(p.mm + 3, 0, 7 * sizeof(unsigned), st));          // running maxima, segment count, flag: zero
   const dim3 block(256);
@@ -775,8 +715,9 @@ extern "C" int spg_prune_reduce(const float* xyz, const uint8_t* rgb, const uint
   if (n_voxels == 0) return 0;
   SPG_CHECK_ARG(out_xyz && out_rgb && out_labels && out_objects, "null output");
   hipStream_t st = (hipStream_t)stream;
-  PruneWs p = prune_carve(workspace, workspace_bytes, n);
-  SPG_CHECK_ARG(p.ok, "workspace too small (spg_prune_workspace_bytes(n))");
+  Carve w(workspace, workspace_bytes);
+  PruneWs p(w, n);
+  SPG_CHECK_ARG(w.ok, "workspace too small (spg_prune_workspace_bytes(n))");
   PruneOut o{out_xyz, out_rgb, out_labels, out_objects, n_labels, n_objects};
   hipLaunchKernelGGL(prune_reduce_kernel, dim3(spg_cdiv(n_voxels, 256)), dim3(256), 0, st, xyz, rgb, labels, objects,
                      (const unsigned*)p.idx_sorted, (const int64_t*)p.seg_off, (const unsigned*)p.order, n_voxels, o, p.flag);

@@ -27,23 +27,11 @@
 //   new_ver_index) and one over the edges (kept edge ids, relabelled ends).
 #include <climits>
 #include <cstring>
-#include <rocprim/rocprim.hpp>
 
 #include "../../include/spg_hip.h"
-#include "spg_common.h"
+#include "spg_part.h"
 
 namespace {
-
-typedef unsigned long long u64;
-
-#define SPG_RP(expr)                                                                      \
-  do {                                                                                    \
-    hipError_t e__ = (expr);                                                              \
-    if (e__ != hipSuccess) {                                                              \
-      spg_set_error("%s:%d: %s: %s", __FILE__, __LINE__, #expr, hipGetErrorString(e__));  \
-      return (int)e__;                                                                    \
-    }                                                                                     \
-  } while (0)
 
 constexpr int TL_BLOCK = 256;
 constexpr int TL_VPB = 32;             // selected vertices per workgroup (include/spg_hip.h: SPG_TILES_VERTICES_PER_BLOCK)
@@ -52,24 +40,6 @@ constexpr int RS_BLOCK = 1024;
 constexpr u64 RS_FREE = ~0ull;
 
 static_assert(TL_VPB == SPG_TILES_VERTICES_PER_BLOCK, "header and kernel disagree");
-
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-struct Carve {
-  char* p;
-  size_t left;
-  bool ok = true;
-  void* take(size_t bytes) {
-    bytes = align256(bytes);
-    if (bytes > left) { ok = false; return nullptr; }
-    void* r = p;
-    p += bytes; left -= bytes;
-    return r;
-  }
-};
-
-// correctly rounded float32 square root (see spg_spgraph.hip: the float64 root rounded once more cannot differ from it)
-__device__ __forceinline__ float sqrt_rn_f32(float x) { return (float)sqrt((double)x); }
 
 // -------------------------------------------------------------------------------------------------------------------
 // neighbourhood tiles
@@ -375,12 +345,26 @@ struct NonZero {
   __device__ int operator()(uint8_t x) const { return x != 0 ? 1 : 0; }
 };
 
-size_t scan_tmp(long m) {
-  size_t b = 0;
-  (void)rocprim::exclusive_scan(nullptr, b, rocprim::make_transform_iterator((const uint8_t*)nullptr, NonZero()), (int*)nullptr, 0, (size_t)m,
-                                rocprim::plus<int>(), (hipStream_t)0);
-  return b;
-}
+struct RandomSubgraphWs {      // per-vertex proposal keys, two frontiers
+  u64* key;
+  int *fr0, *fr1;
+  RandomSubgraphWs(Carve& w, long n) {
+    key = w.take_n<u64>(n);
+    fr0 = w.take_n<int>(n); fr1 = w.take_n<int>(n);
+  }
+};
+
+struct InducedSubgraphWs {     // prefix sums of both masks (E >= 1 here), rocPRIM scratch
+  int *pv, *pe;
+  void* tmp; size_t tmp_bytes;
+  InducedSubgraphWs(Carve& w, long n, long E) {
+    pv = w.take_n<int>(n);
+    pe = w.take_n<int>(E);
+    const auto mask = rocprim::make_transform_iterator((const uint8_t*)nullptr, NonZero());
+    tmp_bytes = std::max(exclusive_scan_bytes<int>(n, mask), exclusive_scan_bytes<int>(E, mask));
+    tmp = w.take(tmp_bytes);
+  }
+};
 
 __global__ void is_vertices_kernel(const uint8_t* __restrict__ sel, const int* __restrict__ pre, long n, int64_t* __restrict__ rows,
                                    int64_t* __restrict__ new_ver_index, int64_t* __restrict__ counts) {
@@ -470,8 +454,9 @@ extern "C" int spg_augment_whole(const float* xyz, const float* rgb, long N, con
 }
 
 extern "C" size_t spg_random_subgraph_workspace_bytes(long n) {
-  n = std::max<long>(n, 1);
-  return align256((size_t)n * 8) + 2 * align256((size_t)n * 4) + 4096;
+  Carve w;
+  RandomSubgraphWs l(w, std::max<long>(n, 1));
+  return w.used();
 }
 
 extern "C" int spg_random_subgraph(const int32_t* rowptr, const uint32_t* inc, const int32_t* ends, long E, long n, int subgraph_size,
@@ -482,10 +467,10 @@ extern "C" int spg_random_subgraph(const int32_t* rowptr, const uint32_t* inc, c
   SPG_CHECK_ARG(n_seeds >= 0 && (n_seeds == 0 || seeds), "bad seeds");
   SPG_CHECK_ARG(rowptr && selected_ver && state && workspace && (E == 0 || (inc && ends && selected_edg)), "bad argument");
   hipStream_t st = (hipStream_t)stream;
-  Carve w{(char*)workspace, workspace_bytes};
-  u64* key = (u64*)w.take((size_t)n * 8);
-  int* fr0 = (int*)w.take((size_t)n * 4);
-  int* fr1 = (int*)w.take((size_t)n * 4);
+  Carve w(workspace, workspace_bytes);
+  RandomSubgraphWs l(w, n);
+  u64* key = l.key;
+  int *fr0 = l.fr0, *fr1 = l.fr1;
   SPG_CHECK_ARG(w.ok, "workspace too small (spg_random_subgraph_workspace_bytes)");
   SPG_RP(hipMemsetAsync(key, 0xFF, (size_t)n * 8, st));
   hipLaunchKernelGGL(rs_kernel, dim3(1), dim3(RS_BLOCK), 0, st, rowptr, inc, ends, (int)n, subgraph_size, seeds, n_seeds, selected_ver, key, fr0, fr1,
@@ -500,8 +485,9 @@ extern "C" int spg_random_subgraph(const int32_t* rowptr, const uint32_t* inc, c
 }
 
 extern "C" size_t spg_induced_subgraph_workspace_bytes(long n, long E) {
-  n = std::max<long>(n, 1); E = std::max<long>(E, 1);
-  return align256((size_t)n * 4) + align256((size_t)E * 4) + align256(std::max(scan_tmp(n), scan_tmp(E))) + 4096;
+  Carve w;
+  InducedSubgraphWs l(w, std::max<long>(n, 1), std::max<long>(E, 1));
+  return w.used();
 }
 
 extern "C" int spg_induced_subgraph(const int32_t* ends, long E, long n, const uint8_t* selected_ver, const uint8_t* selected_edg,
@@ -511,11 +497,11 @@ extern "C" int spg_induced_subgraph(const int32_t* ends, long E, long n, const u
   SPG_CHECK_ARG(selected_ver && rows && new_ver_index && counts && workspace, "bad argument");
   SPG_CHECK_ARG(E == 0 || (ends && selected_edg && kept_edges && edg_source && edg_target), "bad argument");
   hipStream_t st = (hipStream_t)stream;
-  Carve w{(char*)workspace, workspace_bytes};
-  int* pv = (int*)w.take((size_t)n * 4);
-  int* pe = (int*)w.take((size_t)std::max<long>(E, 1) * 4);
-  size_t tmp_bytes = std::max(scan_tmp(n), scan_tmp(std::max<long>(E, 1)));
-  void* tmp = w.take(tmp_bytes);
+  Carve w(workspace, workspace_bytes);
+  InducedSubgraphWs l(w, n, std::max<long>(E, 1));
+  int *pv = l.pv, *pe = l.pe;
+  void* tmp = l.tmp;
+  const size_t tmp_bytes = l.tmp_bytes;
   SPG_CHECK_ARG(w.ok, "workspace too small (spg_induced_subgraph_workspace_bytes)");
   SPG_RP(hipMemsetAsync(counts, 0, 2 * sizeof(int64_t), st));
   size_t b = tmp_bytes;
