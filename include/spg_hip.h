@@ -743,6 +743,28 @@ int spg_induced_subgraph(const int32_t* ends, long E, long n, const uint8_t* sel
                          int64_t* new_ver_index, int64_t* kept_edges, int64_t* edg_source, int64_t* edg_target, int64_t* counts,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the scene structure of the learned partition on the device (csrc/spg_structure.hip; reference supervized_partition/
+ * graph_processing.py:120-190, the arithmetic between prune, the kNN search, connected_comp and compute_geof) ---- */
+enum { SPG_STRUCTURE_IDS_NONE = 0, SPG_STRUCTURE_IDS_OBJECTS = 1, SPG_STRUCTURE_IDS_LABELS = 2, SPG_STRUCTURE_IDS_GIVEN = 3 };
+/* frame f32 [5] (device) = min z, min x, min y, max x, max y of xyz f32 [n, 3], n >= 1.  *error_flag (device int32) is zeroed here;
+ * a coordinate that is NaN or infinite sets its bit 0 (the frame is then meaningless). */
+size_t spg_structure_frame_workspace_bytes(long n);
+int spg_structure_frame(const float* xyz, long n, float* frame, int32_t* error_flag, void* workspace, size_t workspace_bytes, void* stream);
+/* Per vertex, each output optional (null = not made): elevation f32 [n] = z - min z; xyn f32 [n, 2] = (xy - mi) / ((ma - mi) + 1e-8f),
+ * every step in float32 and one correctly rounded division; rgb f32 [n, 3] = rgb_u8 / 255 (both or neither); geof f32 [n, 4]: column 3
+ * doubled IN PLACE; hard_ids i64 [n] by id_mode: OBJECTS = the first arg-max over columns 1 ... hist_cols - 1 of the row of hist
+ * (uint32 [n, hist_cols]; `objects[:, 1:].argmax(1) + 1`, an all-zero row gives 1), LABELS = the first arg-max over all columns (an
+ * all-zero row gives 0), GIVEN = ids_in (int32, or int64 with ids_is_i64) widened, NONE = not written. */
+int spg_structure_vertices(const float* xyz, long n, const float* frame, const uint8_t* rgb_u8, const void* hist, int hist_cols,
+                           int id_mode, const void* ids_in, int ids_is_i64, float* elevation, float* xyn, float* rgb, float* geof,
+                           int64_t* hard_ids, void* stream);
+/* The adjacency of the kNN table knn_idx i32 [n, k_local] (the point itself already dropped): edg_source i64 [n * k_adj] =
+ * repeat(arange(n), k_adj), edg_target = the first k_adj columns; with hard_ids (i64 [n], may be null): is_transition u8 =
+ * id[source] != id[target], active u8 = its complement.  Every entry of the table is checked: one outside [0, n) ORs 2 into
+ * *error_flag (not zeroed here) and is read as 0. */
+int spg_structure_edges(const int32_t* knn_idx, long n, int k_local, int k_adj, const int64_t* hard_ids, int64_t* edg_source,
+                        int64_t* edg_target, uint8_t* is_transition, uint8_t* active, int32_t* error_flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

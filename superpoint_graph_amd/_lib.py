@@ -174,6 +174,10 @@ SIGNATURES = {
     'spg_random_subgraph': (_i, [_p, _p, _p, _l, _l, _i, _p, _i, _p, _p, _p, _p, _sz, _p]),
     'spg_induced_subgraph_workspace_bytes': (_sz, [_l, _l]),
     'spg_induced_subgraph': (_i, [_p, _l, _l, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    'spg_structure_frame_workspace_bytes': (_sz, [_l]),
+    'spg_structure_frame': (_i, [_p, _l, _p, _p, _p, _sz, _p]),
+    'spg_structure_vertices': (_i, [_p, _l, _p, _p, _p, _i, _i, _p, _i, _p, _p, _p, _p, _p, _p]),
+    'spg_structure_edges': (_i, [_p, _l, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
     'spg_edge_features': (_i, [ctypes.POINTER(EdgeFeatureSpecs), _p, _l, _p, _p, _p, _p]),
     'spg_loader_random': (_i, [_p, _p, _p, _i, _i, _i, ctypes.c_uint64, ctypes.c_uint32, _i, ctypes.c_float, _i, ctypes.c_float, _i, _p, _p, _p, _p]),
     'spg_cross_entropy_fwd': (_i, [_p, _p, _p, _i, _i, ctypes.c_int64, _i, _p, _p, _p, _p]),

@@ -1642,3 +1642,88 @@ def induced_subgraph(graph: EdgeGraph, selected_ver, selected_edg):
                                  _ptr(counts), _ptr(ws), ws.numel(), _stream()), 'spg_induced_subgraph')
     m, Ek = (int(v) for v in counts.tolist())
     return rows[:m], new_ver_index, kept[:Ek], src[:Ek], tgt[:Ek]
+
+
+# --------------------------------------------------------------------------------------------------
+# the scene structure of the learned partition (csrc/spg_structure.hip; reference supervized_partition/graph_processing.py:120-190)
+# --------------------------------------------------------------------------------------------------
+_ID_MODES = {'objects': 1, 'labels': 2, 'given': 3}
+
+
+def scene_structure(xyz, knn_idx, k_adj: int, ids=None, hist=None, id_mode='objects', geof=None, rgb=None):
+    """What graph_processing.py:main() computes per file between prune, the kNN search and compute_geof (:126, :144-190), on
+    device tensors: xyz f32 [n, 3]; knn_idx i32 [n, k_local] as ops.knn returns it (the point itself dropped); the first k_adj
+    columns are the adjacency.  The vertex ids that decide is_transition come from
+      id_mode 'objects': hist i32 [n, C] (pruned s3dis objects)  -> hist[:, 1:].argmax(1) + 1,
+      id_mode 'labels':  hist i32 [n, C] (pruned vkitti labels)   -> hist.argmax(1); the objects are then the components over
+                         the edges that are no transition (ops.connected_components: numbered by smallest member),
+      id_mode 'given':   ids integer [n].
+    geof f32 [n, 4] (ops.compute_geof) gets its column 3 doubled IN PLACE (:177); rgb u8 [n, 3] is returned as f32 / 255 (:353).
+    -> dict of device tensors: edg_source, edg_target i64 [n * k_adj], nei (knn_idx itself: adopted, not copied), is_transition
+    u8, hard_ids i64 [n], objects i64 [n], elevation f32 [n] (z - min z), xyn f32 [n, 2], geof, rgb (None when not given), and
+    graph, the EdgeGraph of the adjacency.  Host reads: the error word after the frame pass (ValueError on NaN / infinity before
+    anything else is launched) and after the edges, the EdgeGraph's, and the component count with id_mode 'labels'."""
+    _req(xyz, torch.float32, 'xyz'); _req(knn_idx, torch.int32, 'knn_idx')
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] < 1:
+        raise ValueError(f'scene_structure: xyz must be [n, 3] with n >= 1, got {tuple(xyz.shape)}')
+    n, k_adj = int(xyz.shape[0]), int(k_adj)
+    if knn_idx.dim() != 2 or knn_idx.shape[0] != n:
+        raise ValueError(f'scene_structure: knn_idx must be [{n}, k_local], got {tuple(knn_idx.shape)}')
+    k_local = int(knn_idx.shape[1])
+    if not 1 <= k_adj <= k_local:
+        raise ValueError(f'scene_structure: 1 <= k_adj <= k_local = {k_local} expected, got {k_adj}')
+    if id_mode not in _ID_MODES:
+        raise ValueError(f"scene_structure: id_mode must be 'objects', 'labels' or 'given', got {id_mode!r}")
+    mode, ids_is_i64 = _ID_MODES[id_mode], 0
+    if id_mode == 'given':
+        if ids is None or hist is not None:
+            raise ValueError("scene_structure: id_mode 'given' takes ids (and no hist)")
+        if not torch.is_tensor(ids) or ids.dtype.is_floating_point or ids.dtype == torch.bool or ids.shape != (n,):
+            raise ValueError(f'scene_structure: ids must be an integer tensor [{n}]')
+        if ids.dtype not in (torch.int32, torch.int64):
+            ids = ids.to(torch.int64)
+        _req(ids, None, 'ids')
+        ids_is_i64 = int(ids.dtype == torch.int64)
+    else:
+        if hist is None or ids is not None:
+            raise ValueError(f'scene_structure: id_mode {id_mode!r} takes hist (and no ids)')
+        _req(hist, torch.int32, 'hist')
+        min_cols = 2 if id_mode == 'objects' else 1                  # 'objects' takes its arg-max from column 1 on
+        if hist.dim() != 2 or hist.shape[0] != n or hist.shape[1] < min_cols:
+            raise ValueError(f'scene_structure: hist must be [{n}, C] with C >= {min_cols}, got {tuple(hist.shape)}')
+    if geof is not None:
+        _req(geof, torch.float32, 'geof')
+        if geof.shape != (n, 4):
+            raise ValueError(f'scene_structure: geof must be [{n}, 4], got {tuple(geof.shape)}')
+    if rgb is not None:
+        _req(rgb, torch.uint8, 'rgb')
+        if rgb.shape != (n, 3):
+            raise ValueError(f'scene_structure: rgb must be [{n}, 3], got {tuple(rgb.shape)}')
+    L, dev, st = lib(), xyz.device, _stream()
+    f32, i64, u8 = torch.float32, torch.int64, torch.uint8
+    frame = torch.empty(5, dtype=f32, device=dev)
+    err = torch.empty(1, dtype=torch.int32, device=dev)
+    ws = _u8_workspace(L.spg_structure_frame_workspace_bytes(n), dev)
+    check(L.spg_structure_frame(_ptr(xyz), n, _ptr(frame), _ptr(err), _ptr(ws), ws.numel(), st), 'spg_structure_frame')
+    if int(err.item()) & 1:
+        raise ValueError('Input contains NaN or infinity.')
+    E = n * k_adj
+    out = {'elevation': torch.empty(n, dtype=f32, device=dev), 'xyn': torch.empty(n, 2, dtype=f32, device=dev),
+           'hard_ids': torch.empty(n, dtype=i64, device=dev), 'geof': geof, 'nei': knn_idx,
+           'rgb': torch.empty(n, 3, dtype=f32, device=dev) if rgb is not None else None}
+    check(L.spg_structure_vertices(_ptr(xyz), n, _ptr(frame), _ptr(rgb), _ptr(hist), int(hist.shape[1]) if hist is not None else 0, mode,
+                                   _ptr(ids), ids_is_i64, _ptr(out['elevation']), _ptr(out['xyn']), _ptr(out['rgb']), _ptr(geof),
+                                   _ptr(out['hard_ids']), st), 'spg_structure_vertices')
+    out['edg_source'], out['edg_target'] = torch.empty(E, dtype=i64, device=dev), torch.empty(E, dtype=i64, device=dev)
+    out['is_transition'], active = torch.empty(E, dtype=u8, device=dev), torch.empty(E, dtype=u8, device=dev)
+    check(L.spg_structure_edges(_ptr(knn_idx), n, k_local, k_adj, _ptr(out['hard_ids']), _ptr(out['edg_source']), _ptr(out['edg_target']),
+                                _ptr(out['is_transition']), _ptr(active), _ptr(err), st), 'spg_structure_edges')
+    if int(err.item()) & 2:
+        raise IndexError(f'scene_structure: a neighbour index is outside [0, {n})')
+    out['graph'] = EdgeGraph(out['edg_source'], out['edg_target'], n)
+    if id_mode == 'labels':
+        comp, _, _ = connected_components(out['graph'], active)
+        out['objects'] = comp.to(i64)
+    else:
+        out['objects'] = out['hard_ids']
+    return out

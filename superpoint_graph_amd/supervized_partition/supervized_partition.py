@@ -4,16 +4,28 @@
 transformer `model.stn` and a PointNet without inner transformer `model.ptn`, evaluated together by
 `learning.pointnet.LocalCloudEmbedder`.  The two flags that reach only this embedder are honoured: `ptn_norm`
 ('batch' | 'layer' | 'group') and `ptn_n_group`; module order and state_dict keys are the reference's, so its checkpoints load
-with strict=True.  The training loop itself is not part of this package: it needs cut pursuit, which stays an input."""
+with strict=True.  For the hand-crafted vertex values (ver_value 'geof' / 'geofrgb', learned_embeddings 0: :423-428) the model is
+the reference's single placeholder parameter.  The training loop itself is not part of this package: it needs cut pursuit, which
+stays an input."""
+import torch
 import torch.nn as nn
 
 from ..learning.pointnet import PointNet, STNkD
 
 
 def create_model(args):
-    """-> nn.Module with .stn (if ptn_nfeat_stn > 0) and .ptn.  Only the learned embeddings (ver_value 'ptn') are built."""
+    """-> nn.Module with .stn (if ptn_nfeat_stn > 0) and .ptn for the learned embeddings (ver_value 'ptn'), or with .placeholder
+    alone for ver_value 'geof' / 'geofrgb' (learned_embeddings 0, as the reference's parser derives it from ver_value)."""
     if getattr(args, 'ver_value', 'ptn') in ('geof', 'geofrgb'):
-        raise NotImplementedError("the 'geof' / 'geofrgb' vertex values are not part of this package")
+        if args.learned_embeddings:
+            raise NotImplementedError(f"create_model: ver_value {args.ver_value!r} goes with learned_embeddings 0 (the reference's parser sets "
+                                      "learned_embeddings = 'ptn' in ver_value or ver_value == 'xyz'); the geof values with a learned "
+                                      "embedder are not a model the reference trains")
+        model = nn.Module()
+        model.placeholder = nn.Parameter(torch.tensor(0.0))
+        if getattr(args, 'cuda', 0):
+            model.cuda()
+        return model
     if not args.learned_embeddings or 'ptn' not in args.ptn_embedding:
         raise NotImplementedError("create_model: only the learned embeddings (learned_embeddings = 1, ptn_embedding 'ptn') are built")
     norm, n_group = getattr(args, 'ptn_norm', 'batch'), getattr(args, 'ptn_n_group', 2)
