@@ -464,7 +464,9 @@ int spg_loader_random(const int64_t* counts, const int64_t* ids, const int32_t* 
  * Weighted cross entropy of the training / evaluation loops (learning/main.py:205,255:
  * nn.functional.cross_entropy(outputs, label_mode, weight=class_weights); rows with target == ignore_index do not
  * count): loss (1 float; reduction_mean: sum_i w[t_i] nll_i / sum_i w[t_i], else the plain sum), lse [N] (log-sum-exp
- * per row, kept for the backward), wsum (1 float, the normaliser).  Backward: grad_logits [N, C] from grad_loss (1 float).
+ * per row), wsum (1 float, the normaliser).  Backward: grad_logits [N, C] from grad_loss (1 float) and wsum; it forms each
+ * row's maximum and sum again (exp((x - m) - log s): the rounded sum m + log s would cost ulp(m) / 2 in the exponent) and
+ * does not read lse, which stays in the signature.
  * One launch each, fixed summation order.  A target outside [0, C) that is not ignore_index (torch: device-side assert)
  * makes the loss NaN -- the kernels are asynchronous, so the error surfaces in the value instead of an error code.
  * ---------------------------------------------------------------------------------------------- */

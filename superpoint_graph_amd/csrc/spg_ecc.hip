@@ -1137,7 +1137,8 @@ __device__ __forceinline__ void spg_px_head_accum(const float* wc, int ldw, int 
 }
 
 // One node behind its last iteration: hlog = the finished logit of class `lane` (lanes < C).  Per element the expressions of
-// spg_loss.hip (ce_fwd_bwd_kernel); every lane reads the node's C logits back from LDS and forms the max and the sum of the
+// spg_loss.hip (ce_fwd_bwd_kernel) except that the softmax is exp(x - lse) with lse = m + log s rounded to float32 (spg_loss.hip
+// keeps m and log s apart; the two differ by ulp(m) / 2 in the exponent, round-off at the |x| < 100 of a classifier); every lane reads the node's C logits back from LDS and forms the max and the sum of the
 // exponentials itself, in class order -- ce_fwd_kernel's own loops (no cross-lane reduction on the tail of the launch).
 // d loss / d (module output) = W^T g: column lane + 64 j of the output per lane and j (all states at once: consecutive lanes,
 // consecutive LDS words, the j-th read 256 bytes further), the classes in order.

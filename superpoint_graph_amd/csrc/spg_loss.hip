@@ -22,12 +22,12 @@ __global__ __launch_bounds__(1024) void ce_fwd_kernel(const float* __restrict__ 
     for (int c = 0; c < C; ++c) m = fmaxf(m, x[c]);
     float s = 0.f;
     for (int c = 0; c < C; ++c) s += expf(x[c] - m);
-    const float l = m + logf(s);
-    lse[i] = l;
+    const float ls = logf(s);
+    lse[i] = m + ls;
     const int64_t t = target[i];
     if (t != ignore_index && t >= 0 && t < C) {
       const float w = weight ? weight[t] : 1.f;
-      accl += (double)(w * (l - x[t]));
+      accl += (double)(w * (ls - (x[t] - m)));      // nll = log s - (x_t - m): m + log s rounds at |m| >> 1 and would cancel here
       accw += (double)w;
     } else if (t != ignore_index) {
       s_bad = 1;      // a class index outside [0, C) that is not ignore_index: torch raises a device assert; here the loss becomes NaN
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(1024) void ce_fwd_kernel(const float* __restrict__ 
 }
 
 __global__ void ce_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target, const float* __restrict__ weight,
-                              const float* __restrict__ lse, const float* __restrict__ wsum, const float* __restrict__ grad_loss,
+                              const float* __restrict__ wsum, const float* __restrict__ grad_loss,
                               int N, int C, int64_t ignore_index, int reduction_mean, float* __restrict__ grad_logits) {
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (long)N * C) return;
@@ -53,9 +53,17 @@ __global__ void ce_bwd_kernel(const float* __restrict__ logits, const int64_t* _
   const int64_t t = target[i];
   float g = 0.f;
   if (t != ignore_index && t >= 0 && t < C) {
+    // softmax = exp((x - m) - log s) with the row's maximum and sum formed again by the forward's own loops (C <= 64 values):
+    // the stored lse = m + log s is rounded at the magnitude of m, an absolute error of ulp(m) / 2 in the exponent -- 5e-4
+    // RELATIVE in every gradient of a row whose logits sit at 1e4 (tests/test_gpu_op_edges.py).
+    const float* x = logits + (long)i * C;
+    float m = -FLT_MAX;
+    for (int k = 0; k < C; ++k) m = fmaxf(m, x[k]);
+    float s = 0.f;
+    for (int k = 0; k < C; ++k) s += expf(x[k] - m);
     const float w = weight ? weight[t] : 1.f;
     const float scale = (*grad_loss) * w / (reduction_mean ? *wsum : 1.f);
-    g = scale * (expf(logits[idx] - lse[i]) - (c == (int)t ? 1.f : 0.f));
+    g = scale * (expf((x[c] - m) - logf(s)) - (c == (int)t ? 1.f : 0.f));
   }
   grad_logits[idx] = g;
 }
@@ -73,7 +81,7 @@ __global__ __launch_bounds__(1024) void ce_fwd_bwd_kernel(const float* __restric
   __shared__ double s_l[16], s_w[16];
   __shared__ int s_bad;
   __shared__ float s_wsum;
-  __shared__ float s_lse[CE_ROWS];
+  __shared__ float s_max[CE_ROWS], s_logsum[CE_ROWS];
   if (blockIdx.x == 0) {
     if (threadIdx.x == 0) s_bad = 0;
     __syncthreads();
@@ -84,12 +92,12 @@ __global__ __launch_bounds__(1024) void ce_fwd_bwd_kernel(const float* __restric
       for (int c = 0; c < C; ++c) m = fmaxf(m, x[c]);
       float s = 0.f;
       for (int c = 0; c < C; ++c) s += expf(x[c] - m);
-      const float l = m + logf(s);
-      lse[i] = l;
+      const float ls = logf(s);
+      lse[i] = m + ls;
       const int64_t t = target[i];
       if (t != ignore_index && t >= 0 && t < C) {
         const float w = weight ? weight[t] : 1.f;
-        accl += (double)(w * (l - x[t]));
+        accl += (double)(w * (ls - (x[t] - m)));
         accw += (double)w;
       } else if (t != ignore_index) {
         s_bad = 1;
@@ -130,7 +138,8 @@ __global__ __launch_bounds__(1024) void ce_fwd_bwd_kernel(const float* __restric
     for (int c = 0; c < C; ++c) m = fmaxf(m, x[c]);
     float s = 0.f;
     for (int c = 0; c < C; ++c) s += expf(x[c] - m);
-    s_lse[threadIdx.x] = m + logf(s);
+    s_max[threadIdx.x] = m;
+    s_logsum[threadIdx.x] = logf(s);
   }
   __syncthreads();
   if (reduction_mean) wsum = s_wsum;
@@ -142,7 +151,7 @@ __global__ __launch_bounds__(1024) void ce_fwd_bwd_kernel(const float* __restric
     if (t != ignore_index && t >= 0 && t < C) {
       const float w = weight ? weight[t] : 1.f;
       const float scale = 1.f * w / (reduction_mean ? wsum : 1.f);
-      g = scale * (expf(logits[idx] - s_lse[il]) - (c == (int)t ? 1.f : 0.f));
+      g = scale * (expf((logits[idx] - s_max[il]) - s_logsum[il]) - (c == (int)t ? 1.f : 0.f));
     }
     grad_logits[idx] = g;
   }
@@ -174,7 +183,7 @@ extern "C" int spg_cross_entropy_bwd(const float* logits, const int64_t* target,
                                      int reduction_mean, float* grad_logits, void* stream) {
   SPG_CHECK_ARG(logits && target && lse && wsum && grad_loss && grad_logits && N > 0 && C > 0, "bad argument");
   hipLaunchKernelGGL(ce_bwd_kernel, dim3(spg_cdiv((long)N * C, 256)), dim3(256), 0, (hipStream_t)stream, logits, target, weight,
-                     lse, wsum, grad_loss, N, C, ignore_index, reduction_mean, grad_logits);
+                     wsum, grad_loss, N, C, ignore_index, reduction_mean, grad_logits);      // (lse: an output of the forward, not read)
   SPG_LAUNCH_CHECK();
   return 0;
 }

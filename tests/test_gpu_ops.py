@@ -96,7 +96,7 @@ def test_fused_ecc_32_channels(hip, matrix, n, e):
     assert maxrel(xg.grad, gx_ref) < 2e-6 and maxrel(wg.grad, gw_ref) < 2e-6
 
 
-@pytest.mark.parametrize('layernorm,ingate', [(True, True), (False, False), (True, False)])
+@pytest.mark.parametrize('layernorm,ingate', [(True, True), (False, False), (True, False), (False, True)])
 def test_gru_cell(hip, layernorm, ingate):
     from superpoint_graph_amd.learning import modules
     g = np.load(os.path.join(GOLDEN, 'ops.npz'))
