@@ -181,6 +181,9 @@ typedef struct spg_gn_cfg {
 } spg_gn_cfg;
 
 int spg_gn_check(const spg_gn_cfg* cfg);      /* 0, or -2 with the refused limit in spg_last_error() */
+/* test helper (host only): the wavefronts per workgroup (4, 2 or 1) that the LDS layout of the forward (backward = 0) or of
+ * the backward (backward != 0) allows for this configuration; negative where spg_gn_check refuses it */
+int spg_gn_debug_waves(const spg_gn_cfg* cfg, int backward);
 size_t spg_gn_workspace_bytes(const spg_gn_cfg* cfg, int B);
 size_t spg_gn_bwd_workspace_bytes(const spg_gn_cfg* cfg, int B);
 int spg_gn_forward_ext(const spg_gn_cfg* cfg, int B, const float* clouds, const float* clouds_global, const float* ext_transform,

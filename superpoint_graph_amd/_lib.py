@@ -106,6 +106,7 @@ SIGNATURES = {
     'spg_pointnet_bwd_workspace_bytes': (_sz, [ctypes.POINTER(PointNetCfg), _i]),
     'spg_pointnet_backward': (_i, [ctypes.POINTER(PointNetCfg), _i, _p, _p, c_void_pp, _p, c_void_pp, _p, _p, _p]),
     'spg_gn_check': (_i, [ctypes.POINTER(GnCfg)]),
+    'spg_gn_debug_waves': (_i, [ctypes.POINTER(GnCfg), _i]),
     'spg_gn_workspace_bytes': (_sz, [ctypes.POINTER(GnCfg), _i]),
     'spg_gn_bwd_workspace_bytes': (_sz, [ctypes.POINTER(GnCfg), _i]),
     'spg_gn_forward_ext': (_i, [ctypes.POINTER(GnCfg), _i, _p, _p, _p, c_void_pp, _p, _p, _p]),

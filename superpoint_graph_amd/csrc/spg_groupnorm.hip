@@ -219,9 +219,13 @@ __device__ __forceinline__ void gn_norm_bwd(const Team& t, float* slot, float* G
     const float* yb = Y + rb * rpd * ldy + g * Cg;
     const float rstd = ws0[(long)rb * rec + L.soff + 2 * g + 1], m1 = mstat[2 * d], m2 = mstat[2 * d + 1];
     for (int e = t.lane; e < n; e += 64) {
+      // never contracted: dxh is rounded as in the sums above before m1 is subtracted.  A group of ONE element has dxh == m1 and
+      // xh == 0, and its dz (with everything below it) is then exactly 0; fused, it is rstd times the product's rounding error
+#pragma clang fp contract(off)
       const int p = e / Cg, cc = e - p * Cg, c = g * Cg + cc;
       const float xh = yb[p * ldy + cc];
-      gb[p * ldg + cc] = rstd * (gb[p * ldg + cc] * L.gam[c] - m1 - xh * m2);
+      const float dxh = gb[p * ldg + cc] * L.gam[c];
+      gb[p * ldg + cc] = rstd * ((dxh - m1) - xh * m2);
     }
   }
   team_sync(t);
@@ -637,6 +641,12 @@ extern "C" int spg_gn_check(const spg_gn_cfg* cfg) {
   GnPlan f, b;
   SPG_TRY(gn_plan(cfg, 1, false, f));
   return gn_plan(cfg, 1, true, b);
+}
+
+extern "C" int spg_gn_debug_waves(const spg_gn_cfg* cfg, int backward) {
+  GnPlan pl;
+  const int rc = gn_plan(cfg, 1, backward != 0, pl);
+  return rc == 0 ? pl.nw : rc;
 }
 
 extern "C" size_t spg_gn_workspace_bytes(const spg_gn_cfg* cfg, int B) {
