@@ -770,6 +770,24 @@ int spg_structure_vertices(const float* xyz, long n, const float* frame, const u
 int spg_structure_edges(const int32_t* knn_idx, long n, int k_local, int k_adj, const int64_t* hard_ids, int64_t* edg_source,
                         int64_t* edg_target, uint8_t* is_transition, uint8_t* active, int32_t* error_flag, void* stream);
 
+/* ---- the ground-plane elevation of the learned partition on the device (csrc/spg_plane.hip; reference supervized_partition/
+ * graph_processing.py:181-186: sklearn's RANSACRegressor(random_state=0) on the points less than 0.5 above the lowest one, restated:
+ * DESIGN.md section 4.11g).  Error word (device int32): bit 0 a coordinate is NaN or infinite, bit 1 no trial was accepted (no
+ * consensus set), bit 2 a subset index lies outside [0, n_low). ---- */
+/* the workspace of spg_plane_low (n_low < 0; trials ignored) or of spg_plane_fit (n_low >= 0) */
+size_t spg_plane_workspace_bytes(long n, long n_low, int trials);
+/* low_index i32 [n] (device): the first *n_low entries are the indices, ascending, of the points with (z - min z) < low_height in
+ * float32; n_low: device int32.  *error_flag is zeroed here; bit 0 as above (low_index is then meaningless). */
+int spg_plane_low(const float* xyz, long n, float low_height, int32_t* low_index, int32_t* n_low, int32_t* error_flag, void* workspace,
+                  size_t workspace_bytes, void* stream);
+/* subsets i32 [trials, 3] (device, 1 <= trials <= 1024): indices into the n_low >= 3 low points.  -> elevation f32 [n], coef f64 [2],
+ * intercept f64 [1], threshold f32 [1] = median(|y - median(y)|) of the low points' z in float32, inlier_mask u8 [n_low] of the best
+ * trial, result i32 [2] = (number of trials the acceptance loop consumed, best trial or -1).  ORs bits 1 / 2 into *error_flag (not
+ * zeroed here); with bit 1 the coefficients and the elevation are NaN. */
+int spg_plane_fit(const float* xyz, long n, const int32_t* low_index, long n_low, const int32_t* subsets, int trials, float* elevation,
+                  double* coef, double* intercept, float* threshold, uint8_t* inlier_mask, int32_t* result, int32_t* error_flag,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

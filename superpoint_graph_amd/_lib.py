@@ -179,6 +179,9 @@ SIGNATURES = {
     'spg_structure_frame': (_i, [_p, _l, _p, _p, _p, _sz, _p]),
     'spg_structure_vertices': (_i, [_p, _l, _p, _p, _p, _i, _i, _p, _i, _p, _p, _p, _p, _p, _p]),
     'spg_structure_edges': (_i, [_p, _l, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
+    'spg_plane_workspace_bytes': (_sz, [_l, _l, _i]),
+    'spg_plane_low': (_i, [_p, _l, ctypes.c_float, _p, _p, _p, _p, _sz, _p]),
+    'spg_plane_fit': (_i, [_p, _l, _p, _l, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     'spg_edge_features': (_i, [ctypes.POINTER(EdgeFeatureSpecs), _p, _l, _p, _p, _p, _p]),
     'spg_loader_random': (_i, [_p, _p, _p, _i, _i, _i, ctypes.c_uint64, ctypes.c_uint32, _i, ctypes.c_float, _i, ctypes.c_float, _i, _p, _p, _p, _p]),
     'spg_cross_entropy_fwd': (_i, [_p, _p, _p, _i, _i, ctypes.c_int64, _i, _p, _p, _p, _p]),

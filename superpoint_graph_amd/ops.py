@@ -6,6 +6,7 @@ from __future__ import annotations
 import ctypes
 from typing import List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1726,4 +1727,86 @@ def scene_structure(xyz, knn_idx, k_adj: int, ids=None, hist=None, id_mode='obje
         out['objects'] = comp.to(i64)
     else:
         out['objects'] = out['hard_ids']
+    return out
+
+
+# --------------------------------------------------------------------------------------------------
+# the ground-plane elevation (csrc/spg_plane.hip; reference supervized_partition/graph_processing.py:181-186, learning/s3dis_dataset.py:130-133)
+# --------------------------------------------------------------------------------------------------
+PLANE_MAX_TRIALS = 1024
+
+
+def ransac_subsets(n_low: int, trials: int = 100, seed: int = 0):
+    """The first `trials` triples that sklearn's RANSACRegressor(random_state=seed) draws from n_low samples: the stream of
+    sample_without_replacement(n_low, 3, random_state=np.random.RandomState(seed)) -> int64 [trials, 3] (host).  n_low >= 300
+    (3 / n_low <= 0.01): tracking selection, randint(n_low) until three distinct values; 4 <= n_low <= 299: permutation(n_low)[:3];
+    n_low == 3: (0, 1, 2) without a draw.  sklearn draws lazily, one triple per trial: this is a prefix of the same stream."""
+    n_low, trials = int(n_low), int(trials)
+    if n_low < 3:
+        raise ValueError(f'`min_samples` may not be larger than number of samples: n_samples = {n_low}.')
+    rs = np.random.RandomState(seed)
+    out = np.empty((trials, 3), np.int64)
+    for t in range(trials):
+        if n_low == 3:
+            out[t] = (0, 1, 2)
+        elif n_low < 300:
+            out[t] = rs.permutation(n_low)[:3]
+        else:
+            sel = []
+            while len(sel) < 3:
+                j = int(rs.randint(n_low))
+                if j not in sel:
+                    sel.append(j)
+            out[t] = sel
+    return out
+
+
+def plane_elevation(xyz, subsets=None, seed: int = 0, max_trials: int = 100, low_height: float = 0.5):
+    """The elevation of graph_processing.py:181-186 with plane_model: z minus the plane that sklearn 1.7's
+    RANSACRegressor(random_state=seed) fits to the points less than low_height above the lowest one, restated on the device
+    (csrc/spg_plane.hip): xyz f32 [n, 3] on the device -> dict: elevation f32 [n], coef f64 [2],
+    intercept f64 (0-d), threshold f32 (0-d: median |y - median y| in float32, numpy's bits), low_index i32 [n_low], inlier_mask u8
+    [n_low] (device tensors) and the host ints n_low, n_trials (what sklearn's n_trials_ counts), best_trial.
+    subsets: integer [T, 3], indices into the low points, one triple per trial (T <= 1024 replaces max_trials); None draws
+    ransac_subsets(n_low, max_trials, seed) on the host.  Every trial is evaluated; sklearn's acceptance loop is replayed on the
+    device.  Host reads: n_low with the error word (ValueError on NaN / infinity before anything else), and the error word with
+    n_trials / best_trial at the end (ValueError when no trial found a consensus set, IndexError for a subset index)."""
+    _req(xyz, torch.float32, 'xyz')
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] < 1:
+        raise ValueError(f'plane_elevation: xyz must be [n, 3] with n >= 1, got {tuple(xyz.shape)}')
+    L, dev, st = lib(), xyz.device, _stream()
+    n = int(xyz.shape[0])
+    low_index = torch.empty(n, dtype=torch.int32, device=dev)
+    head = torch.empty(2, dtype=torch.int32, device=dev)                   # n_low, error word: one read
+    ws = _u8_workspace(L.spg_plane_workspace_bytes(n, -1, 0), dev)
+    check(L.spg_plane_low(_ptr(xyz), n, float(low_height), _ptr(low_index), _ptr(head), _ptr(head[1:]), _ptr(ws), ws.numel(), st), 'spg_plane_low')
+    n_low, err = (int(v) for v in head.tolist())
+    if err & 1:
+        raise ValueError('Input contains NaN or infinity.')
+    if n_low < 3:
+        raise ValueError(f'`min_samples` may not be larger than number of samples: n_samples = {n_low}.')
+    if subsets is None:
+        if not 1 <= int(max_trials) <= PLANE_MAX_TRIALS:
+            raise ValueError(f'plane_elevation: 1 <= max_trials <= {PLANE_MAX_TRIALS} expected, got {max_trials}')
+        subsets = ransac_subsets(n_low, int(max_trials), seed)
+    if not torch.is_tensor(subsets):
+        subsets = torch.from_numpy(np.ascontiguousarray(np.asarray(subsets)))
+    if subsets.dtype.is_floating_point or subsets.dim() != 2 or subsets.shape[1] != 3 or not 1 <= subsets.shape[0] <= PLANE_MAX_TRIALS:
+        raise ValueError(f'plane_elevation: subsets must be an integer array [T, 3] with 1 <= T <= {PLANE_MAX_TRIALS}')
+    subsets = subsets.to(device=dev, dtype=torch.int32).contiguous()
+    T = int(subsets.shape[0])
+    out = {'elevation': torch.empty(n, dtype=torch.float32, device=dev), 'coef': torch.empty(2, dtype=torch.float64, device=dev),
+           'intercept': torch.empty((), dtype=torch.float64, device=dev), 'threshold': torch.empty((), dtype=torch.float32, device=dev),
+           'low_index': low_index[:n_low], 'inlier_mask': torch.empty(n_low, dtype=torch.uint8, device=dev)}
+    tail = torch.zeros(3, dtype=torch.int32, device=dev)                   # n_trials, best_trial, error word
+    ws = _u8_workspace(L.spg_plane_workspace_bytes(n, n_low, T), dev)
+    check(L.spg_plane_fit(_ptr(xyz), n, _ptr(low_index), n_low, _ptr(subsets), T, _ptr(out['elevation']), _ptr(out['coef']), _ptr(out['intercept']),
+                          _ptr(out['threshold']), _ptr(out['inlier_mask']), _ptr(tail), _ptr(tail[2:]), _ptr(ws), ws.numel(), st), 'spg_plane_fit')
+    n_trials, best, err = (int(v) for v in tail.tolist())
+    if err & 4:
+        raise IndexError(f'plane_elevation: a subset index is outside [0, {n_low})')
+    if err & 2:
+        raise ValueError('RANSAC could not find a valid consensus set. All `max_trials` iterations were skipped because each randomly chosen '
+                         'sub-sample failed the passing criteria.')
+    out.update(n_low=n_low, n_trials=n_trials, best_trial=best)
     return out

@@ -321,9 +321,11 @@ def build_structure(xyz, rgb, labels, objects, args, dataset, n_labels, n_object
     None reads objects.max() back as the reference does), the vertex's object is the arg-max of its histogram from column 1 on;
     without pruning the objects are taken as given.  dataset 'vkitti': prunes with labels only, hard label = arg-max of the label histogram, objects =
     the components of constant hard label (without pruning, labels must already be a histogram i32 [n, C]).  Then one kNN self
-    query with k_nn_local, compute_geof on that table, ops.scene_structure.  elevation f32 [n of the pruned cloud]: used as it is
-    (plane_model = 1 needs it: the RANSAC plane is not part of this package).  Nothing is read back but the words the ops
-    read (voxel count, error words, component count)."""
+    query with k_nn_local, compute_geof on that table, ops.scene_structure.  elevation: with plane_model = 1 (the reference's default)
+    either 'ransac' -- the height above the RANSAC ground plane of the (pruned) cloud, ops.plane_elevation (:181-186) -- or an array
+    f32 [n of the pruned cloud], used as it is; None asks the caller to choose (NotImplementedError).  With plane_model = 0 'ransac'
+    and None both give z - min z (:188).  Nothing is read back but the words the ops read (voxel count, low-point count, error words,
+    trial counters, component count)."""
     a = types.SimpleNamespace(**{k: getattr(args, k, v) for k, v in STRUCTURE_DEFAULTS.items()})
     k_local, k_adj = int(a.k_nn_local), int(a.k_nn_adj)
     if dataset not in ('s3dis', 'vkitti', 'sema3d'):
@@ -334,8 +336,8 @@ def build_structure(xyz, rgb, labels, objects, args, dataset, n_labels, n_object
     if a.use_voronoi > 0:
         raise NotImplementedError('build_structure: use_voronoi > 0 needs the Delaunay adjacency (qhull), which is not part of this package')
     if a.plane_model and elevation is None:
-        raise NotImplementedError('build_structure: plane_model = 1 fits the ground plane with RANSAC (sklearn), which is not part of this '
-                                  'package; pass elevation= (used as it is) or plane_model = 0')
+        raise NotImplementedError("build_structure: plane_model = 1 fits the ground plane with RANSAC; pass elevation='ransac' (the fit of "
+                                  "ops.plane_elevation on the device), an elevation array (used as it is) or plane_model = 0")
     if k_local > ops.KNN_MAX_K:
         raise NotImplementedError(f'build_structure: k_nn_local = {k_local} exceeds the device kNN limit ops.KNN_MAX_K = {ops.KNN_MAX_K}')
     if not 1 <= k_adj <= k_local:
@@ -373,6 +375,10 @@ def build_structure(xyz, rgb, labels, objects, args, dataset, n_labels, n_object
     n = int(xyz.shape[0])
     if n <= k_local:
         raise ValueError(f'Expected n_neighbors <= n_samples, but n_samples = {n}, n_neighbors = {k_local + 1}')
+    if isinstance(elevation, str):
+        if elevation != 'ransac':
+            raise ValueError(f"build_structure: elevation must be 'ransac', an array or None, got {elevation!r}")
+        elevation = ops.plane_elevation(xyz)['elevation'] if a.plane_model else None                            # :181-186
     if elevation is not None:
         elevation = _device_array(elevation, np.float32, torch.float32, dev, 'elevation').reshape(-1)
         if elevation.shape[0] != n:
