@@ -788,6 +788,32 @@ int spg_plane_fit(const float* xyz, long n, const int32_t* low_index, long n_low
                   double* coef, double* intercept, float* threshold, uint8_t* inlier_mask, int32_t* result, int32_t* error_flag,
                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- parsed superpoint clouds on the device (csrc/spg_parsed.hip; the per-scene body of the reference's preprocess_pointclouds,
+ * learning/{s3dis,sema3d,vkitti,custom}_dataset.py, restated: DESIGN.md section 4.11h).  Error word (device int32): bit 0 a
+ * coordinate is NaN or infinite, bit 1 a component index lies outside [0, n), bit 2 a trim position lies outside [0, size). ---- */
+enum { SPG_PARSED_S3DIS = 0, SPG_PARSED_SEMA3D = 1, SPG_PARSED_VKITTI = 2 };      /* 15, 11 (also `custom`), 14 columns */
+size_t spg_parsed_workspace_bytes(long n);
+/* Scene statistics of xyz f32 [n, 3], n >= 1, by fixed-order reductions without atomics (the same input gives the same bits):
+ * stats_f32 [6] = min x, y, z, max x, y, z; stats_f64 [5] = mean x, y, z (float64 sums), then with with_distance the mean and the
+ * population standard deviation of d = sqrt((x - mean x)^2 + (y - mean y)^2) in float64 (two more passes; NaN otherwise);
+ * centroid f32 [3] = the means rounded once.  All on the device.  *error_flag is zeroed here; bit 0 as above. */
+int spg_parsed_stats(const float* xyz, long n, int with_distance, float* stats_f32, double* stats_f64, float* centroid,
+                     int32_t* error_flag, void* workspace, size_t workspace_bytes, void* stream);
+/* points f32 [n_rows, ncols]: the rows of component 0, 1, ... back to back.  out_off / src_off: device int64 [n_comp + 1], ascending
+ * from 0; component c owns comp_idx[src_off[c] ... src_off[c + 1]) (int32, or int64 with idx_is_i64; src_off[n_comp] entries at
+ * least) and output rows out_off[c] ... out_off[c + 1].  Row j of an untrimmed component comes from vertex comp_idx[src_off[c] + j];
+ * with trim_off[c] >= 0 (device int64 [n_comp], -1 = not trimmed; null with trim = nothing is trimmed) from comp_idx[src_off[c] +
+ * trim[trim_off[c] + j]].  rgb: uint8 [n, 3], or float32 with rgb_is_f32.  geof f32 [n, 4] (null for VKITTI).  S3DIS: elevation f32
+ * [n] or null (z / 4 - 0.5), lpsv_raw: geof unchanged instead of geof - 0.5; stats_* from spg_parsed_stats (with_distance for S3DIS;
+ * not read by SEMA3D).  ORs bits 1 / 2 into *error_flag (not zeroed here); such an index is read as 0. */
+int spg_parsed_rows(int recipe, const float* xyz, long n, const void* rgb, int rgb_is_f32, const float* geof, const float* elevation,
+                    int lpsv_raw, const float* stats_f32, const double* stats_f64, const int64_t* out_off, const int64_t* src_off,
+                    long n_comp, const void* comp_idx, int idx_is_i64, const int32_t* trim, const int64_t* trim_off, long n_rows,
+                    float* points, int32_t* error_flag, void* stream);
+/* count i64 [n_classes] (device, zeroed here) = bincount(argmax(labels[:, 1:], 1), minlength = n_classes) of labels uint32 (int32 with
+ * labels_signed) [n, n_classes + 1]: the first maximum; an all-zero row counts for class 0.  1 <= n_classes <= 4096. */
+int spg_class_count(const void* labels, int labels_signed, long n, int n_classes, int64_t* count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -546,11 +546,22 @@ class DevicePointCache:
     touch of a scene uploads its ragged point buffer once; afterwards a training step only sends indices."""
 
     def __init__(self, store, device):
+        """store: the point store the first touch of a scene reads, or None for a cache that holds only what `put` registered."""
         self._store, self._dev, self._scenes = store, device, {}
+
+    def put(self, fname, parsed):
+        """Registers a scene parsed on the device (learning/parsed.py: preprocess_scene -> ParsedScene): its rows are served as they
+        are, nothing is copied."""
+        dev = torch.device(self._dev)
+        if parsed.points.device.type != dev.type or (dev.index is not None and parsed.points.device.index != dev.index):
+            raise ValueError(f'DevicePointCache.put: the scene lives on {parsed.points.device}, the cache on {self._dev}')
+        self._scenes[fname] = (parsed.points, np.asarray(parsed.offsets, dtype=np.int64), {i: k for k, i in enumerate(parsed.ids)})
 
     def scene(self, fname):
         ent = self._scenes.get(fname)
         if ent is None:
+            if self._store is None:
+                raise KeyError(f'DevicePointCache: scene {fname!r} was not put and the cache has no store to read it from')
             ids = self._store.ids(fname)
             arrs = [np.asarray(self._store.points(fname, i), dtype=np.float32) for i in ids]
             off = np.zeros(len(ids) + 1, dtype=np.int64)

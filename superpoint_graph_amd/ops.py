@@ -1810,3 +1810,126 @@ def plane_elevation(xyz, subsets=None, seed: int = 0, max_trials: int = 100, low
                          'sub-sample failed the passing criteria.')
     out.update(n_low=n_low, n_trials=n_trials, best_trial=best)
     return out
+
+
+# --------------------------------------------------------------------------------------------------
+# parsed superpoint clouds (csrc/spg_parsed.hip; reference learning/{s3dis,sema3d,vkitti,custom}_dataset.py: preprocess_pointclouds)
+# --------------------------------------------------------------------------------------------------
+PARSED_RECIPES = {'s3dis': (0, 15), 'sema3d': (1, 11), 'custom': (1, 11), 'vkitti': (2, 14)}      # name -> (SPG_PARSED_*, columns)
+CLASS_COUNT_MAX = 4096
+
+
+def scene_stats(xyz, with_distance: bool = False):
+    """The statistics preprocess_pointclouds takes of a scene, by fixed-order reductions (the same input gives the same bits):
+    xyz f32 [n, 3] on the device -> (stats_f32 [6] = min x, y, z, max x, y, z; stats_f64 [5] = mean x, y, z and, with_distance,
+    the mean and population standard deviation of the distance to the room centre in float64; centroid f32 [3]), device tensors.
+    One host read: the error word (ValueError on NaN / infinity)."""
+    _req(xyz, torch.float32, 'xyz')
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] < 1:
+        raise ValueError(f'scene_stats: xyz must be [n, 3] with n >= 1, got {tuple(xyz.shape)}')
+    L, dev, n = lib(), xyz.device, int(xyz.shape[0])
+    s32, s64 = torch.empty(6, dtype=torch.float32, device=dev), torch.empty(5, dtype=torch.float64, device=dev)
+    centroid, err = torch.empty(3, dtype=torch.float32, device=dev), torch.empty(1, dtype=torch.int32, device=dev)
+    ws = _u8_workspace(L.spg_parsed_workspace_bytes(n), dev)
+    check(L.spg_parsed_stats(_ptr(xyz), n, int(bool(with_distance)), _ptr(s32), _ptr(s64), _ptr(centroid), _ptr(err), _ptr(ws), ws.numel(),
+                             _stream()), 'spg_parsed_stats')
+    if int(err.item()) & 1:
+        raise ValueError('Input contains NaN or infinity.')
+    return s32, s64, centroid
+
+
+def parsed_points(recipe, xyz, rgb, comp_off, comp_idx, geof=None, elevation=None, trim=None, lpsv_raw: bool = False):
+    """The datasets preprocess_pointclouds writes for one scene, as one device buffer (csrc/spg_parsed.hip, DESIGN.md section
+    4.11h).  recipe 's3dis' (15 columns: xyz, rgb, e, lpsv[4], xyzn[3], dist), 'sema3d' / 'custom' (11: xyz, rgb, z / 100,
+    geof - 0.5) or 'vkitti' (14: xyz, rgb, e, four zeros, xyzn).  xyz f32 [n, 3]; rgb u8 | f32 [n, 3]; geof f32 [n, 4] (not for
+    vkitti); s3dis: elevation f32 [n] or None (z / 4 - 0.5), lpsv_raw: geof unchanged (supervized_partition).  Component c owns
+    comp_idx[comp_off[c] : comp_off[c + 1]] (comp_off i64 [C + 1], host or device; comp_idx i32 | i64 [M] on the device; a vertex
+    may appear in no component or in several).  trim: {component: positions inside it (integer sequence)} -- the component's rows
+    are then comp_idx[comp_off[c] + positions], in that order.
+    -> points f32 [Ntot, ncols] with the rows of component 0, 1, ... back to back, centroid f32 [3] (device), offsets i64 [C + 1]
+    (host numpy).  Host traffic: comp_off down when it lives on the device, the offset and trim tables up, two reads of the error
+    word (ValueError for NaN / infinity, IndexError for a component index or a trim position out of range)."""
+    if recipe not in PARSED_RECIPES:
+        raise ValueError(f'parsed_points: recipe must be one of {sorted(PARSED_RECIPES)}, got {recipe!r}')
+    code, ncols = PARSED_RECIPES[recipe]
+    _req(xyz, torch.float32, 'xyz')
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] < 1:
+        raise ValueError(f'parsed_points: xyz must be [n, 3] with n >= 1, got {tuple(xyz.shape)}')
+    n, dev = int(xyz.shape[0]), xyz.device
+    _req(rgb, None, 'rgb')
+    if rgb.dtype not in (torch.uint8, torch.float32) or rgb.shape != (n, 3):
+        raise ValueError(f'parsed_points: rgb must be uint8 or float32 [{n}, 3]')
+    if code != 2:
+        if geof is None:
+            raise ValueError(f'parsed_points: recipe {recipe!r} needs geof')
+        _req(geof, torch.float32, 'geof')
+        if geof.shape != (n, 4):
+            raise ValueError(f'parsed_points: geof must be [{n}, 4], got {tuple(geof.shape)}')
+    else:
+        geof = None
+    if elevation is not None:
+        if code != 0:
+            raise ValueError("parsed_points: only recipe 's3dis' takes an elevation")
+        _req(elevation, torch.float32, 'elevation')
+        if elevation.shape != (n,):
+            raise ValueError(f'parsed_points: elevation must be [{n}], got {tuple(elevation.shape)}')
+    _req(comp_idx, None, 'comp_idx')
+    if comp_idx.dtype not in (torch.int32, torch.int64) or comp_idx.dim() != 1:
+        raise ValueError('parsed_points: comp_idx must be int32 or int64 [M]')
+    M = int(comp_idx.numel())
+    src_h = (comp_off.cpu().numpy() if torch.is_tensor(comp_off) else np.asarray(comp_off)).astype(np.int64).reshape(-1)
+    C = len(src_h) - 1
+    if C < 1 or src_h[0] != 0 or src_h[-1] > M or (np.diff(src_h) < 0).any():
+        raise ValueError(f'parsed_points: comp_off must be [C + 1] with C >= 1, ascending from 0 to at most {M}')
+    sizes = np.diff(src_h)
+    out_sizes, trim_off_h, trim_parts, n_trim = sizes.copy(), None, [], 0
+    if trim:
+        trim_off_h = np.full(C, -1, np.int64)
+        for c in sorted(trim):
+            pos = np.asarray(trim[c])
+            if not 0 <= int(c) < C or pos.ndim != 1 or pos.dtype.kind not in 'iu':
+                raise ValueError(f'parsed_points: trim maps a component in [0, {C}) to a 1-d integer array')
+            if pos.size and (pos.max() >= 2 ** 31 or pos.min() < -2 ** 31):
+                raise IndexError(f'parsed_points: a trim position of component {c} is outside [0, {int(sizes[c])})')
+            trim_off_h[c], out_sizes[c] = n_trim, pos.size
+            trim_parts.append(pos.astype(np.int32))
+            n_trim += pos.size
+    off_h = np.zeros(C + 1, np.int64)
+    np.cumsum(out_sizes, out=off_h[1:])
+    n_rows = int(off_h[-1])
+    if n_rows >= 2 ** 31 - 1:
+        raise ValueError('parsed_points: fewer than 2^31 - 1 rows expected')
+    L, st = lib(), _stream()
+    s32, s64, centroid = scene_stats(xyz, code == 0)        # (sema3d reads no statistic: the centroid and the finite check)
+    out_off_d, src_off_d = torch.from_numpy(off_h).to(dev), torch.from_numpy(src_h).to(dev)
+    trim_off_d = trim_d = None
+    if trim_off_h is not None:          # (one spare entry: the table is never empty)
+        trim_off_d, trim_d = torch.from_numpy(trim_off_h).to(dev), torch.from_numpy(np.concatenate(trim_parts + [np.zeros(1, np.int32)])).to(dev)
+    points = torch.empty(n_rows, ncols, dtype=torch.float32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(L.spg_parsed_rows(code, _ptr(xyz), n, _ptr(rgb), int(rgb.dtype == torch.float32), _ptr(geof), _ptr(elevation), int(bool(lpsv_raw)),
+                            _ptr(s32), _ptr(s64), _ptr(out_off_d), _ptr(src_off_d), C, _ptr(comp_idx), int(comp_idx.dtype == torch.int64),
+                            _ptr(trim_d), _ptr(trim_off_d), n_rows, _ptr(points), _ptr(err), st), 'spg_parsed_rows')
+    flag = int(err.item())
+    if flag & 2:
+        raise IndexError(f'parsed_points: a component index is outside [0, {n})')
+    if flag & 4:
+        raise IndexError('parsed_points: a trim position is outside its component')
+    return points, centroid, off_h
+
+
+def class_count(labels, n_classes: int):
+    """np.bincount(np.argmax(labels[:, 1:], 1), minlength=n_classes) of the label histograms labels u32 | i32 [n, n_classes + 1] on
+    the device (first maximum; an all-zero row counts for class 0) -> i64 [n_classes] on the device."""
+    n_classes = int(n_classes)
+    _req(labels, None, 'labels')
+    if labels.dtype not in (torch.int32, torch.uint32):
+        raise TypeError(f'class_count: labels must be uint32 or int32, got {labels.dtype}')
+    if not 1 <= n_classes <= CLASS_COUNT_MAX:
+        raise ValueError(f'class_count: 1 <= n_classes <= {CLASS_COUNT_MAX} expected, got {n_classes}')
+    if labels.dim() != 2 or labels.shape[1] != n_classes + 1:
+        raise ValueError(f'class_count: labels must be [n, {n_classes + 1}], got {tuple(labels.shape)}')
+    count = torch.empty(n_classes, dtype=torch.int64, device=labels.device)
+    check(lib().spg_class_count(_ptr(labels), int(labels.dtype == torch.int32), int(labels.shape[0]), n_classes, _ptr(count), _stream()),
+          'spg_class_count')
+    return count
