@@ -1,9 +1,10 @@
 """The persistent, dataflow-synchronised form of the GRU recurrence (spg_ecc_persist_{fwd,bwd}_kernel: all iterations in one
 launch, neighbour states exchanged as tagged granules) against the per-iteration launches it replaces (spg_tune key 8): the two
 forms execute the same arithmetic in the same order, so outputs and every gradient must be BIT-IDENTICAL -- a stale or torn
-hand-off shows up as a difference.  Graph shapes: the BASELINE scene size, hubs with more in-/out-edges than the
-register-resident filters (8) and than one gather pass (32), isolated nodes, a partial last workgroup; repeated launches with the
-GPU busy in between (uneven load), and the time-out counter must stay 0.  The oracle comparison of the same module is
+hand-off shows up as a difference.  Graph shapes: the BASELINE scene size, hubs with more in-/out-edges than the register-resident
+filters (12 with one workgroup per CU; 6 forward / 2 backward with two) and than one gather pass (32), isolated nodes, a partial
+last workgroup; repeated launches with the GPU busy in between (uneven load), and the time-out counter must stay 0.  The oracle
+comparison of the same module is
 tests/test_gpu_model.py::test_rnn_ecc_module_large_graph_vs_oracle (7000 nodes: per-iteration path) and the golden tests
 (<= 49 nodes: persistent path)."""
 import numpy as np
@@ -21,7 +22,7 @@ def _graph(n, e, seed, hubs=True):
     if hubs and n > 100:
         tgt[:70] = 3                      # in-degree >= 70: more than two gather passes
         src[70:150] = 5                   # out-degree >= 80
-        tgt[150:162] = 9                  # between the resident filters (8) and one pass (32)
+        tgt[150:162] = 9                  # at the resident filters (12 / 6 / 2) and below one pass (32)
         tgt[tgt == 11] = 12               # node 11: no in-edges
         src[src == 13] = 14               # node 13: no out-edges
     order = np.argsort(tgt, kind='stable')
