@@ -3,7 +3,7 @@
 // The network-level entry points live in spg_pointnet.hip and spg_eccnet.hip.
 #include "../../include/spg_hip.h"
 #include "spg_ecc.h"
-#include "spg_gemm.h"
+#include "spg_dense.h"
 
 extern "C" int spg_version(void) { return SPG_VERSION; }
 
@@ -323,16 +323,15 @@ extern "C" int spg_gru_cell_bwd(const float* input, const float* hidden, const f
   p.hin = hidden; p.ld = 32; p.agg = input; p.ldagg = 32; p.Gcur = grad_input; p.ldg = 32;
   p.dgi = dgi; p.dgh = dgh; p.dui = dui; p.duh = duh; p.ld96 = 96; p.dpre = dpre; p.xg = xg; p.ld32 = 32;
   SPG_TRY(spg_launch_ecc_step_bwd(p, st));
-  auto ident = [](const float* X, long ld) { SpgOperand o; memset(&o, 0, sizeof(o)); o.mode = SPG_PRO_IDENT; o.X = X; o.ld = ld; return o; };
   SpgWgradParams w; memset(&w, 0, sizeof(w));
   w.M = n; w.N = 96; w.K = 32;
-  if (grads[0]) { w.a = ident(dgi, 96); w.b = ident(xg, 32); SPG_TRY(spg_launch_wgrad(w, grads[0], work, st)); }
-  if (grads[1]) { w.a = ident(dgh, 96); w.b = ident(hidden, 32); SPG_TRY(spg_launch_wgrad(w, grads[1], work, st)); }
+  if (grads[0]) { w.a = spg_op_ident(dgi, 96); w.b = spg_op_ident(xg, 32); SPG_TRY(spg_launch_wgrad(w, grads[0], work, st)); }
+  if (grads[1]) { w.a = spg_op_ident(dgh, 96); w.b = spg_op_ident(hidden, 32); SPG_TRY(spg_launch_wgrad(w, grads[1], work, st)); }
   if (grads[2]) SPG_TRY(spg_launch_colsum(dui, 96, n, 96, grads[2], work, st));
   if (grads[3]) SPG_TRY(spg_launch_colsum(duh, 96, n, 96, grads[3], work, st));
   if (ingate) {
     w.N = 32;
-    if (grads[4]) { w.a = ident(dpre, 32); w.b = ident(hidden, 32); SPG_TRY(spg_launch_wgrad(w, grads[4], work, st)); }
+    if (grads[4]) { w.a = spg_op_ident(dpre, 32); w.b = spg_op_ident(hidden, 32); SPG_TRY(spg_launch_wgrad(w, grads[4], work, st)); }
     if (grads[5]) SPG_TRY(spg_launch_colsum(dpre, 32, n, 32, grads[5], work, st));
   }
   return 0;
@@ -383,16 +382,15 @@ extern "C" int spg_lstm_cell_bwd(const float* input, const float* h, const float
     p.use_dcdir = 1;
   }
   SPG_TRY(spg_launch_ecc_step_bwd(p, st));
-  auto ident = [](const float* X, long ld) { SpgOperand o; memset(&o, 0, sizeof(o)); o.mode = SPG_PRO_IDENT; o.X = X; o.ld = ld; return o; };
   SpgWgradParams w; memset(&w, 0, sizeof(w));
   w.M = n; w.N = 128; w.K = 32;
-  if (grads[0]) { w.a = ident(dgi, 128); w.b = ident(xg, 32); SPG_TRY(spg_launch_wgrad(w, grads[0], work, st)); }
-  if (grads[1]) { w.a = ident(dgh, 128); w.b = ident(h, 32); SPG_TRY(spg_launch_wgrad(w, grads[1], work, st)); }
+  if (grads[0]) { w.a = spg_op_ident(dgi, 128); w.b = spg_op_ident(xg, 32); SPG_TRY(spg_launch_wgrad(w, grads[0], work, st)); }
+  if (grads[1]) { w.a = spg_op_ident(dgh, 128); w.b = spg_op_ident(h, 32); SPG_TRY(spg_launch_wgrad(w, grads[1], work, st)); }
   if (grads[2]) SPG_TRY(spg_launch_colsum(dgi, 128, n, 128, grads[2], work, st));
   if (grads[3]) SPG_TRY(spg_launch_colsum(dgh, 128, n, 128, grads[3], work, st));
   if (ingate) {
     w.N = 32;
-    if (grads[4]) { w.a = ident(dpre, 32); w.b = ident(h, 32); SPG_TRY(spg_launch_wgrad(w, grads[4], work, st)); }
+    if (grads[4]) { w.a = spg_op_ident(dpre, 32); w.b = spg_op_ident(h, 32); SPG_TRY(spg_launch_wgrad(w, grads[4], work, st)); }
     if (grads[5]) SPG_TRY(spg_launch_colsum(dpre, 32, n, 32, grads[5], work, st));
   }
   return 0;
@@ -402,11 +400,7 @@ extern "C" int spg_lstm_cell_bwd(const float* input, const float* h, const float
 // fused dense layer
 // ---------------------------------------------------------------------------------------------
 static SpgOperand affine_operand(const float* X, long ld, int K, const float* sc, const float* sh, int relu) {
-  SpgOperand o; memset(&o, 0, sizeof(o));
-  if (sc == nullptr && !relu) { o.mode = SPG_PRO_IDENT; }
-  else { o.mode = SPG_PRO_AFFINE; o.c0 = sc; o.c1 = sh; o.relu = relu; o.n_affine = K; }
-  o.X = X; o.ld = ld;
-  return o;
+  return (sc == nullptr && !relu) ? spg_op_ident(X, ld) : spg_op_affine(X, ld, K, sc, sh, relu);
 }
 
 extern "C" int spg_linear_fwd(const float* X, long ldx, int M, int K, const float* W, const float* bias, int N,
@@ -450,6 +444,7 @@ extern "C" int spg_linear_wgrad(const float* dY, long lddy, const float* X, long
 
 // weight AND bias gradient of a dense layer in two launches (weight-gradient partials with the column sums of dY riding
 // along, one batched reduction) instead of four (spg_linear_wgrad + spg_colsum)
+// (its own, smaller formula -- not spg_queue_layer_floats: the bias always rides here, no separate column-sum job is ever queued)
 extern "C" size_t spg_linear_wgrad_bias_work_floats(int M, int N, int K) {
   return ((spg_wgrad_workspace_floats(M, N, K) + 63) & ~(size_t)63) + ((spg_wgrad_colsum_floats(M, N, K) + 63) & ~(size_t)63) + 128;
 }

@@ -8,35 +8,11 @@
 // contiguous for the per-edge filter gradient (summed over the iterations in registers, written once).
 #include "../../include/spg_hip.h"
 #include "spg_ecc.h"
-#include "spg_gemm.h"
+#include "spg_dense.h"
 #include <memory>
 #include <vector>
 
 namespace {
-
-struct FLayer {
-  int cin = 0, cout = 0;
-  bool bn = false, relu = false;
-  const float *W = nullptr, *b = nullptr, *gamma = nullptr, *beta = nullptr;
-  float *rm = nullptr, *rv = nullptr;
-  float* y = nullptr;
-  float *mean = nullptr, *rstd = nullptr, *s = nullptr, *t = nullptr;
-  unsigned long long *slots = nullptr, *slots_bwd = nullptr;   // train mode: fixed-point statistics slots (SpgBnFold, spg_gemm.h)
-  float *dW = nullptr, *db = nullptr, *dgamma = nullptr, *dbeta = nullptr;
-};
-
-struct Carver {
-  char* base;
-  size_t off = 0;
-  explicit Carver(void* b) : base((char*)b) {}
-  template <typename T>
-  T* take(size_t n) {
-    off = (off + 255) & ~(size_t)255;
-    T* p = base ? (T*)(base + off) : nullptr;
-    off += n * sizeof(T);
-    return p;
-  }
-};
 
 struct Plan {
   spg_eccrnn_cfg cfg;
@@ -45,7 +21,7 @@ struct Plan {
   int GW = 96;                  // gate rows of the cell: 96 (GRU) / 128 (LSTM)
   bool lstm = false;
   bool training = false;
-  std::vector<FLayer> F;
+  std::vector<SpgDenseLayer> F;
   bool fold = false;            // train mode: the BatchNorm statistics travel as fixed-point slots from producer to consumer GEMM
   bool px = false;              // the persistent (one launch for all iterations) GRU recurrence is applicable: rounds in `groups`
   SpgPxGroups groups;
@@ -71,21 +47,16 @@ int make_plan(const spg_eccrnn_cfg* cfg, int N, int E, int training, void* ws, c
   pl.ldS = (long)(pl.R + 1) * 32;
   pl.nout = c.matrix ? 1024 : 32;
   SPG_CHECK_ARG(c.fnet_widths[c.n_fnet] == pl.nout, "filter network output width must be nc*nc (matrix) or nc (vector)");
-  Carver cv(ws);
-  pl.F.assign(c.n_fnet, FLayer());
+  SpgCarver cv(ws);
+  pl.F.assign(c.n_fnet, SpgDenseLayer());
   int cmax = 4;
   for (int i = 0; i < c.n_fnet; ++i) {
-    FLayer& l = pl.F[i];
+    SpgDenseLayer& l = pl.F[i];
     l.cin = c.fnet_widths[i]; l.cout = c.fnet_widths[i + 1];
     l.bn = (c.bnidx == i); l.relu = i < c.n_fnet - 1;
+    l.ldw = l.cin; l.ldy = l.cout;
     cmax = l.cout > cmax ? l.cout : cmax;
-    if (params) {
-      const void* const* g = params + 6 * i;
-      l.W = (const float*)g[0]; l.b = (const float*)g[1]; l.gamma = (const float*)g[2]; l.beta = (const float*)g[3];
-      l.rm = (float*)g[4]; l.rv = (float*)g[5];
-      SPG_CHECK_ARG(l.W != nullptr, "missing filter-network weight");
-      SPG_CHECK_ARG(!l.bn || (l.rm && l.rv), "missing BatchNorm running statistics");
-    }
+    if (params) SPG_TRY(spg_dense_bind_params(l, params + 6 * i));
     l.y = cv.take<float>((size_t)(E > 0 ? E : 1) * l.cout);
     if (l.bn) {
       l.mean = cv.take<float>(l.cout); l.rstd = cv.take<float>(l.cout);
@@ -124,33 +95,9 @@ int make_plan(const spg_eccrnn_cfg* cfg, int N, int E, int training, void* ws, c
   return 0;
 }
 
-SpgOperand op_ident(const float* X, long ld) {
-  SpgOperand o; memset(&o, 0, sizeof(o));
-  o.mode = SPG_PRO_IDENT; o.X = X; o.ld = ld;
-  return o;
-}
-
 SpgOperand fnet_input(const Plan& pl, int i, const float* edgefeats) {
-  if (i == 0) return op_ident(edgefeats, pl.F[0].cin);
-  const FLayer& p = pl.F[i - 1];
-  SpgOperand o; memset(&o, 0, sizeof(o));
-  o.mode = SPG_PRO_AFFINE; o.X = p.y; o.ld = p.cout; o.relu = p.relu ? 1 : 0; o.n_affine = p.cout;
-  if (p.bn) { o.c0 = p.s; o.c1 = p.t; }
-  return o;
-}
-
-SpgOperand op_bnbwd(const float* dz, const float* y, long ld, const float* consts, int C) {
-  SpgOperand o; memset(&o, 0, sizeof(o));
-  o.mode = SPG_PRO_BNBWD; o.X = dz; o.X2 = y; o.ld = ld;
-  o.c0 = consts; o.c1 = consts + C; o.c2 = consts + 2 * C; o.c3 = consts + 3 * C;
-  return o;
-}
-
-int zero_async(void* p, size_t bytes, hipStream_t st) {
-  if (p == nullptr || bytes == 0) return 0;
-  hipError_t e = hipMemsetAsync(p, 0, bytes, st);
-  if (e != hipSuccess) { spg_set_error("hipMemsetAsync: %s", hipGetErrorString(e)); return (int)e; }
-  return 0;
+  if (i == 0) return spg_op_ident(edgefeats, pl.F[0].cin);
+  return spg_op_affine(pl.F[i - 1], pl.F[i - 1].y, pl.F[i - 1].ldy);
 }
 
 struct BwdScratch {
@@ -165,7 +112,7 @@ struct BwdScratch {
 };
 
 void carve_bwd(const Plan& pl, void* ws, BwdScratch& s) {
-  Carver cv(ws);
+  SpgCarver cv(ws);
   const size_t rows = (size_t)pl.N * (pl.R + 1);
   s.G = cv.take<float>(rows * 32);
   s.dgi = cv.take<float>(rows * pl.GW); s.dgh = cv.take<float>(rows * pl.GW);
@@ -178,15 +125,13 @@ void carve_bwd(const Plan& pl, void* ws, BwdScratch& s) {
   s.dWts = cv.take<float>(Er * pl.nout);
   int cmax = 4;
   size_t wmax = 96 * 32, workmax = 16;
-  for (const FLayer& l : pl.F) {
+  for (const SpgDenseLayer& l : pl.F) {
     cmax = l.cout > cmax ? l.cout : cmax; cmax = l.cin > cmax ? l.cin : cmax;
     wmax = (size_t)l.cin * l.cout > wmax ? (size_t)l.cin * l.cout : wmax;
-    workmax += ((spg_wgrad_workspace_floats(Er, l.cout, l.cin) + 63) & ~(size_t)63) + 64 * (size_t)l.cout + 128 +
-               ((spg_wgrad_colsum_floats((long)Er, l.cout, l.cin) + 63) & ~(size_t)63);
+    workmax += spg_queue_layer_floats((long)Er, l.cout, l.cin);
   }
   // GRU: three weight gradients + three bias column sums over all (node, iteration) rows
-  const size_t work2max = 16 + 3 * (((spg_wgrad_workspace_floats((long)rows, pl.GW, 32) + 63) & ~(size_t)63) + 64 * (size_t)pl.GW + 128 +
-                                    ((spg_wgrad_colsum_floats((long)rows, pl.GW, 32) + 63) & ~(size_t)63));
+  const size_t work2max = 16 + 3 * spg_queue_layer_floats((long)rows, pl.GW, 32);
   int hmax = 4;   // widest hidden activation
   for (int i = 0; i + 1 < (int)pl.F.size(); ++i) hmax = pl.F[i].cout > hmax ? pl.F[i].cout : hmax;
   s.dzA = cv.take<float>(Er * hmax); s.dzB = cv.take<float>(Er * hmax);
@@ -205,10 +150,22 @@ extern "C" size_t spg_eccrnn_workspace_bytes(const spg_eccrnn_cfg* cfg, int N, i
   return pl.bytes;
 }
 
-// train-mode BatchNorm of the filter network without finalize launches, like PointNet's (spg_gemm.h: SpgBnFold): not with
-// synchronised BatchNorm (the ranks' all-reduce sits between producer and consumer), not beyond the slots' capacity
-static bool fnet_fold(const Plan& pl) {
-  return pl.training && !spg_sync_bn_active() && !spg_tune_get(SPG_TUNE_NO_BN_FOLD) && (long)spg_cdiv(pl.E > 0 ? pl.E : 1, SPG_FC_ROWS) * spg_slot_sync_world() <= SPG_FOLD_MAX_CONTRIBUTIONS;
+// train-mode BatchNorm of the filter network without finalize launches (spg_dense.h): one contribution per 32-edge tile.
+// The slot-synchronised check needs an edge: an edge-less rank is refused by the forward's own checks.
+static int fnet_fold(Plan& pl) {
+  pl.fold = pl.training && spg_bn_fold_allowed(spg_cdiv(pl.E > 0 ? pl.E : 1, SPG_FC_ROWS));
+  for (const SpgDenseLayer& l : pl.F)
+    SPG_TRY(spg_bn_slot_sync_check(pl.training && pl.E > 0 && l.bn, pl.fold, "slot-synchronised BatchNorm needs the filter network's statistics slots (spg_tune key 10 off, edges within the slots' capacity on every rank)"));
+  return 0;
+}
+
+// the BatchNorm side of one pass over the E edges (spg_dense.h)
+static SpgDenseBn fnet_bn(const Plan& pl, int bn_update_times, float* stat, float* consts) {
+  SpgDenseBn bn;
+  bn.training = pl.training; bn.fold = pl.fold; bn.update_times = bn_update_times;
+  bn.momentum = pl.cfg.bn_momentum; bn.eps = pl.cfg.bn_eps;
+  bn.stat = stat; bn.stat_cnt = pl.stat_cnt; bn.consts = consts;
+  return bn;
 }
 
 // ---- filter-generating network (once per forward, shared by all iterations): one stage per layer; each stage issues its
@@ -218,43 +175,19 @@ static void fnet_forward_stages(const Plan& pl0, const float* edgefeats, int bn_
   for (int i = 0; i < (int)plan->F.size(); ++i) {
     out.push_back([plan, i, edgefeats, bn_update_times](hipStream_t st) -> int {
       const Plan& pl = *plan;
-      const FLayer& l = pl.F[i];
+      const SpgDenseLayer& l = pl.F[i];
       if (i == 0 && pl.fold)                 // the statistics slots of both directions: cleared launches before their first use
-        for (const FLayer& f : pl.F)
+        for (const SpgDenseLayer& f : pl.F)
           if (f.bn) {
             // BatchNorm behind the FIRST layer (--fnet_bnidx 0 is legal, learning/graphnet.py:17-37): this very stage's GEMM is the
             // slots' first producer, so a zero job in the same group would race with it -- clear them in stream order instead
-            if (&f == &pl.F[0]) SPG_TRY(zero_async(f.slots, sizeof(float) * 2 * spg_fold_slot_words(f.cout), st));
+            if (&f == &pl.F[0]) SPG_TRY(spg_zero_bytes_async(f.slots, sizeof(float) * 2 * spg_fold_slot_words(f.cout), st));
             else SPG_TRY(spg_group_zero(reinterpret_cast<float*>(f.slots), 2 * spg_fold_slot_words(f.cout), st));
             SPG_TRY(spg_group_zero(reinterpret_cast<float*>(f.slots_bwd), 2 * spg_fold_slot_words(f.cout), st));
           }
-      SpgGemmParams g; memset(&g, 0, sizeof(g));
-      g.a = fnet_input(pl, i, edgefeats);
-      g.W = l.W; g.ldw = l.cin; g.bias = l.b; g.M = pl.E; g.N = l.cout; g.K = l.cin; g.rows_per_tile = SPG_FC_ROWS;
-      g.epi = SPG_EPI_FWD; g.Y = l.y; g.ldy = l.cout;
-      g.stat = (l.bn && pl.training) ? pl.stat : nullptr; g.stat_cnt = pl.stat_cnt;
-      if (l.bn && pl.fold) { g.stat = nullptr; g.stat_slots = l.slots; }
-      if (i > 0 && pl.F[i - 1].bn && pl.fold) {      // the producer's statistics are finished in this launch's prologue
-        const FLayer& p = pl.F[i - 1];
-        SpgBnFold f; memset(&f, 0, sizeof(f));
-        f.slots = p.slots; f.C = p.cout; f.update_times = bn_update_times; f.momentum = pl.cfg.bn_momentum; f.eps = pl.cfg.bn_eps;
-        f.count = (double)pl.E; f.gamma = p.gamma; f.beta = p.beta; f.rm = p.rm; f.rv = p.rv;
-        f.mean = p.mean; f.rstd = p.rstd; f.s = p.s; f.t = p.t;
-        g.fold = f;
-      }
-      int nparts = 0;
-      {
-        // a finalize launch behind the GEMM (synchronised BatchNorm / fold switched off): the GEMM must not wait in a group
-        SpgGroupBypass direct(l.bn && !pl.fold && pl.training);
-        SPG_TRY(spg_launch_gemm(g, st, &nparts));
-      }
-      if (l.bn && !pl.fold) {
-        if (pl.training)
-          SPG_TRY(spg_launch_bn_finalize(pl.stat, pl.stat_cnt, nparts, pl.E, l.cout, l.gamma, l.beta, l.rm, l.rv,
-                                         pl.cfg.bn_momentum, pl.cfg.bn_eps, bn_update_times, l.mean, l.rstd, l.s, l.t, nullptr, st));
-        else
-          SPG_TRY(spg_launch_bn_eval(l.cout, l.gamma, l.beta, l.rm, l.rv, pl.cfg.bn_eps, l.s, l.t, st));
-      }
+      SPG_TRY(spg_dense_forward(l, i > 0 ? &pl.F[i - 1] : nullptr, fnet_input(pl, i, edgefeats), pl.E, pl.E,
+                                fnet_bn(pl, bn_update_times, pl.stat, nullptr), nullptr, st));
+      if (l.bn && !pl.training) SPG_TRY(spg_launch_bn_eval(l.cout, l.gamma, l.beta, l.rm, l.rv, pl.cfg.bn_eps, l.s, l.t, st));
       return 0;
     });
   }
@@ -289,7 +222,7 @@ static int eccrnn_recurrent_forward(Plan& pl, const void* graph_ws, const float*
     SPG_TRY(spg_gather_rows(sc->emb, 32, sc->slot_of_row, N, 32, sc->desc, 32, (void*)st));
     h0 = sc->desc;
   }
-  if (pl.fsave_tag != nullptr) SPG_TRY(zero_async(pl.fsave_tag, sizeof(unsigned), st));      // per-iteration path: nothing was kept
+  if (pl.fsave_tag != nullptr) SPG_TRY(spg_zero_bytes_async(pl.fsave_tag, sizeof(unsigned), st));      // per-iteration path: nothing was kept
   SPG_TRY(spg_launch_copy2d(h0, 32, pl.states, pl.ldS, N, 32, st));
   for (int r = 0; r < pl.R; ++r) {
     SpgEccStepFwd p; memset(&p, 0, sizeof(p));
@@ -315,17 +248,11 @@ int spg_eccrnn_forward_phase(const spg_eccrnn_cfg* cfg, int N, int E, const void
   hipStream_t st = (hipStream_t)stream;
   Plan pl;
   SPG_TRY(make_plan(cfg, N, E, training, workspace, params, pl));
-  pl.fold = fnet_fold(pl);
-  // (as spg_pointnet.hip: with slot-synchronised BatchNorm the statistics MUST travel through the slots -- a rank that dropped to
-  //  per-rank finalize statistics because its own edge count exceeds the slots' capacity, or because spg_tune key 10 is set, would
-  //  issue a different number of slot all-reduces than its peers: a hang, or an unsynchronised model)
-  if (pl.training && spg_slot_sync_active() && E > 0)
-    for (const FLayer& l : pl.F)
-      SPG_CHECK_ARG(!l.bn || pl.fold, "slot-synchronised BatchNorm needs the filter network's statistics slots (spg_tune key 10 off, edges within the slots' capacity on every rank)");
+  SPG_TRY(fnet_fold(pl));
   if (E == 0 && pl.training && spg_slot_sync_active())
-    for (const FLayer& l : pl.F) SPG_CHECK_ARG(!l.bn, "slot-synchronised BatchNorm: a rank with an edge-less batch cannot take part in the filter-network statistics");
+    for (const SpgDenseLayer& l : pl.F) SPG_CHECK_ARG(!l.bn, "slot-synchronised BatchNorm: a rank with an edge-less batch cannot take part in the filter-network statistics");
   if (E == 0 && pl.training && spg_sync_bn_active())
-    for (const FLayer& l : pl.F)      // the other ranks enter the layer's all-reduce: skipping it here would hang the job
+    for (const SpgDenseLayer& l : pl.F)      // the other ranks enter the layer's all-reduce: skipping it here would hang the job
       SPG_CHECK_ARG(!l.bn, "synchronised BatchNorm: a rank with an edge-less batch cannot take part in the filter-network statistics");
   if (phase != 2 && E > 0) {
     std::vector<SpgStage> stages;
@@ -354,7 +281,7 @@ extern "C" long spg_eccrnn_debug_offset(const spg_eccrnn_cfg* cfg, int N, int E,
   Plan pl;
   char* fake = (char*)(uintptr_t)4096;
   if (make_plan(cfg, N, E, training, fake, nullptr, pl) != 0 || layer < 0 || layer >= (int)pl.F.size()) return -1;
-  const FLayer& l = pl.F[layer];
+  const SpgDenseLayer& l = pl.F[layer];
   const void* p = what == 0 ? (const void*)l.y : what == 1 ? l.s : l.t;
   return p == nullptr ? -1 : (long)((const char*)p - fake);
 }
@@ -390,15 +317,15 @@ void eccrnn_backward_tail_stages(std::shared_ptr<BwdCtx> c, std::vector<SpgStage
     Plan& pl = c->pl; BwdScratch& s = c->s;
     const int R = pl.R, GW = pl.GW, rows = pl.N * (R + 1);
     SpgWgradParams w; memset(&w, 0, sizeof(w));
-    w.a = op_ident(s.dgi, GW); w.b = op_ident(s.xg, 32); w.M = rows; w.N = GW; w.K = 32;
+    w.a = spg_op_ident(s.dgi, GW); w.b = spg_op_ident(s.xg, 32); w.M = rows; w.N = GW; w.K = 32;
     SPG_TRY(spg_queue_wgrad(c->rq2, w, pl.cell_grads[0], st));
-    w.a = op_ident(s.dgh, GW); w.b = op_ident(pl.states, 32);
+    w.a = spg_op_ident(s.dgh, GW); w.b = spg_op_ident(pl.states, 32);
     SPG_TRY(spg_queue_wgrad(c->rq2, w, pl.cell_grads[1], st));
     // GRU: the biases are added behind the row normalisation; LSTM: in front of it
     SPG_TRY(spg_queue_colsum(c->rq2, pl.lstm ? s.dgi : s.dui, GW, rows, GW, pl.cell_grads[2], st));
     SPG_TRY(spg_queue_colsum(c->rq2, pl.lstm ? s.dgh : s.duh, GW, rows, GW, pl.cell_grads[3], st));
     if (pl.cfg.ingate) {
-      w.a = op_ident(s.dpre, 32); w.b = op_ident(pl.states, 32); w.N = 32;
+      w.a = spg_op_ident(s.dpre, 32); w.b = spg_op_ident(pl.states, 32); w.N = 32;
       // the input gate's bias gradient = column sums of dpre: as their own small job, not riding along with the weight
       // gradient -- the body that carries them needs more than 128 registers and would push the whole group (2700 small
       // workgroups) to the 2-workgroups-per-CU build of the grouped kernel (spg_gemm.hip)
@@ -420,7 +347,7 @@ void eccrnn_backward_tail_stages(std::shared_ptr<BwdCtx> c, std::vector<SpgStage
     if (extra_leaf && extra_with < 0) SPG_TRY(extra_leaf(st));
     if (leaf_with < 0) SPG_TRY(cell_grads(st));
     if (pl.E == 0) {   // no edges: the filter network received no gradient
-      for (FLayer& l : pl.F) {
+      for (SpgDenseLayer& l : pl.F) {
         SPG_TRY(spg_group_zero(l.dW, (size_t)l.cin * l.cout, st));
         SPG_TRY(spg_group_zero(l.db, (size_t)l.cout, st));
         SPG_TRY(spg_group_zero(l.dgamma, (size_t)l.cout, st));
@@ -430,63 +357,26 @@ void eccrnn_backward_tail_stages(std::shared_ptr<BwdCtx> c, std::vector<SpgStage
     }
     // per-edge filter gradients (sum over the iterations): the head of the filter network's chain
     SPG_TRY(spg_launch_ecc_edge_wgrad(c->gr, pl.cfg.matrix, pl.states, ldS, s.G, ldS, R, s.dWts, st));
-    c->cur = op_ident(s.dWts, pl.nout);
+    c->cur = spg_op_ident(s.dWts, pl.nout);
     return 0;
   });
   for (int i = (int)c->pl.F.size() - 1; i >= 0 && c->pl.E > 0; --i) {
     out.push_back([c, i, cell_grads, leaf_with, extra_leaf, extra_with](hipStream_t st) -> int {
       Plan& pl = c->pl; BwdScratch& s = c->s;
       const int E = pl.E;
-      FLayer& l = pl.F[i];
+      SpgDenseLayer& l = pl.F[i];
       if (i == leaf_with) SPG_TRY(cell_grads(st));
       if (extra_leaf && i == extra_with) SPG_TRY(extra_leaf(st));
       const SpgOperand cur = c->cur;
-      const SpgBnFoldBwd fold_i = c->pending;
-      memset(&c->pending, 0, sizeof(c->pending));
-      SpgWgradParams w; memset(&w, 0, sizeof(w));
-      w.a = cur; w.b = fnet_input(pl, i, c->edgefeats); w.M = E; w.N = l.cout; w.K = l.cin;
-      w.fold = fold_i;
-      const bool bias_rides = l.db != nullptr && !l.bn && cur.mode == SPG_PRO_IDENT;      // bias gradient = column sums of `cur`
-      SPG_TRY(spg_queue_wgrad(c->rq, w, l.dW, st, bias_rides ? l.db : nullptr));
-      if (l.db && !bias_rides) {
-        if (l.bn) SPG_TRY(spg_group_zero(l.db, (size_t)l.cout, st));
-        else SPG_TRY(spg_queue_colsum(c->rq, cur.X, cur.ld, E, l.cout, l.db, st));
+      SpgDenseDgrad d;
+      if (i > 0) {
+        float* dzb[2] = {s.dzA, s.dzB};
+        d.prod = &pl.F[i - 1]; d.out = dzb[c->flip]; d.ldout = l.cin; d.Yp = d.prod->y; d.ldyp = d.prod->ldy; d.count = E;
+        d.folds = true;      // (the weight gradient of this layer may run in the same grouped launch: both finish the constants)
+        c->flip ^= 1;
       }
-      if (i == 0) return 0;
-      FLayer& prod = pl.F[i - 1];
-      float* dzb[2] = {s.dzA, s.dzB};
-      float* out = dzb[c->flip]; c->flip ^= 1;
-      SpgGemmParams g; memset(&g, 0, sizeof(g));
-      g.a = cur; g.W = l.W; g.ldw = l.cin; g.w_red = 1;
-      g.M = E; g.N = l.cin; g.K = l.cout; g.rows_per_tile = SPG_FC_ROWS;
-      g.epi = SPG_EPI_BWD; g.Y = out; g.ldy = l.cin; g.Yp = prod.y; g.ldyp = prod.cout;
-      g.mask_relu = prod.relu ? 1 : 0; g.n_mask = prod.cout;
-      g.fold_bwd = fold_i;      // (the weight gradient of this layer may run in the same grouped launch: both finish the constants)
-      const bool fin = prod.bn && !pl.fold;      // finalize launch behind the data gradient: it must not wait in a group
-      if (prod.bn) {
-        g.ms = prod.s; g.mt = prod.t; g.mmean = prod.mean; g.mrstd = prod.rstd; g.stat = s.stat;
-        if (pl.fold) { g.stat = nullptr; g.stat_slots = prod.slots_bwd; }
-      }
-      int nparts = 0;
-      {
-        SpgGroupBypass direct(fin);
-        SPG_TRY(spg_launch_gemm(g, st, &nparts));
-      }
-      if (prod.bn) {
-        if (fin) {
-          SPG_TRY(spg_launch_bn_bwd_finalize(s.stat, nparts, l.cin, E, prod.cout, prod.s, prod.mean, prod.rstd,
-                                             s.consts, prod.dgamma, prod.dbeta, nullptr, st));
-        } else {
-          SpgBnFoldBwd f; memset(&f, 0, sizeof(f));
-          f.slots = prod.slots_bwd; f.C = prod.cout; f.count = (double)E; f.s = prod.s; f.mean = prod.mean; f.rstd = prod.rstd;
-          if (spg_slot_sync_active()) f.grad_mul = 1.0 / (double)spg_slot_sync_world();
-          f.consts = s.consts; f.dgamma = prod.dgamma; f.dbeta = prod.dbeta;
-          c->pending = f;
-        }
-        c->cur = op_bnbwd(out, prod.y, prod.cout, s.consts, prod.cout);
-      } else {
-        c->cur = op_ident(out, l.cin);
-      }
+      SPG_TRY(spg_dense_backward(c->rq, l, cur, fnet_input(pl, i, c->edgefeats), E, d, fnet_bn(pl, 1, s.stat, s.consts), c->pending, nullptr, st));
+      if (i > 0) c->cur = d.prod->bn ? spg_op_bnbwd(d.out, d.prod->y, d.prod->ldy, s.consts, d.prod->cout) : spg_op_ident(d.out, l.cin);
       return 0;
     });
   }
@@ -514,14 +404,8 @@ int spg_eccrnn_backward_phase(const spg_eccrnn_cfg* cfg, int N, int E, const voi
   auto c = std::make_shared<BwdCtx>();
   Plan& pl = c->pl;
   SPG_TRY(make_plan(cfg, N, E, 1, workspace, params, pl));
-  pl.fold = fnet_fold(pl);
-  if (spg_slot_sync_active() && E > 0)
-    for (const FLayer& l : pl.F)
-      SPG_CHECK_ARG(!l.bn || pl.fold, "slot-synchronised BatchNorm needs the filter network's statistics slots (spg_tune key 10 off, edges within the slots' capacity on every rank)");
-  for (int i = 0; i < (int)pl.F.size(); ++i) {
-    void* const* g = grads + 6 * i;
-    pl.F[i].dW = (float*)g[0]; pl.F[i].db = (float*)g[1]; pl.F[i].dgamma = (float*)g[2]; pl.F[i].dbeta = (float*)g[3];
-  }
+  SPG_TRY(fnet_fold(pl));
+  for (size_t i = 0; i < pl.F.size(); ++i) spg_dense_bind_grads(pl.F[i], grads + 6 * i);
   for (int k = 0; k < 6; ++k) pl.cell_grads[k] = (float*)grads[6 * pl.F.size() + k];
   BwdScratch& s = c->s;
   carve_bwd(pl, bwd_workspace, s);
@@ -557,7 +441,7 @@ int spg_eccrnn_backward_phase(const spg_eccrnn_cfg* cfg, int N, int E, const voi
   if (head != nullptr && !persistent)      // (the per-iteration fallback: the loss from the head's logits, as its own launch)
     SPG_TRY(spg_cross_entropy_fwd(head->logits, head->target, head->class_weight, N, head->C, head->ignore_index, head->reduction_mean,
                                   head->loss, head->lse, head->wsum, stream));
-  if (!persistent) SPG_TRY(zero_async(bwd_workspace, s.zero_bytes, st));
+  if (!persistent) SPG_TRY(spg_zero_bytes_async(bwd_workspace, s.zero_bytes, st));
   for (int r = R - 1; r >= 0 && !persistent; --r) {
     SpgEccStepBwd p; memset(&p, 0, sizeof(p));
     p.g = gr; p.W = pl.F.back().y; p.matrix = pl.cfg.matrix;

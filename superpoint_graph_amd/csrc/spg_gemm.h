@@ -243,6 +243,8 @@ bool spg_bwdpair_supported(const SpgGemmParams& g, const SpgOperand& b);
 int spg_queue_bwdpair(SpgReduceQueue& q, SpgGemmParams g, const SpgOperand& b, float* dW, hipStream_t stream);
 int spg_queue_partials(SpgReduceQueue& q, int nsplit, int n, float* out, float** partial, hipStream_t stream);
 int spg_queue_colsum(SpgReduceQueue& q, const float* X, long ld, long M, int N, float* out, hipStream_t stream);
+// arena floats one layer's {spg_queue_wgrad (+ db), or spg_queue_wgrad + spg_queue_colsum} take from a queue
+size_t spg_queue_layer_floats(long M, int N, int K);
 int spg_flush_reduce(SpgReduceQueue& q, hipStream_t stream);
 // jobs whose partials are complete (in stream order) but whose summation may wait for the next batched reduction of this
 // thread: spg_flush_reduce takes them along; spg_flush_deferred_reduce sums what is still waiting (no-op when nothing is)

@@ -1882,6 +1882,14 @@ static int queue_take(SpgReduceQueue& q, size_t floats, float** out, hipStream_t
   return 0;
 }
 
+// Arena floats that cover everything one layer's backward queues over M rows (every queue_take rounds up to 64): the split
+// partials of its weight gradient (spg_queue_wgrad), and for the bias EITHER the per-split column sums riding along with them
+// OR a separate spg_queue_colsum job (<= SPG_COLSUM_SLICES = 64 slices of N floats); + 128 floats of rounding slack.
+size_t spg_queue_layer_floats(long M, int N, int K) {
+  const auto al64 = [](size_t v) { return (v + 63) & ~(size_t)63; };
+  return al64(spg_wgrad_workspace_floats(M, N, K)) + 64 * (size_t)N + 128 + al64(spg_wgrad_colsum_floats(M, N, K));
+}
+
 // room for `nsplit` partials of `n` floats each in the queue's arena + the job that sums them into `out` (the caller's kernel writes
 // the partials: in stream order before the queue is flushed)
 int spg_queue_partials(SpgReduceQueue& q, int nsplit, int n, float* out, float** partial, hipStream_t stream) {

@@ -15,7 +15,7 @@
 //   max of the normalised value -- BatchNorm is monotone per channel).
 #include "../../include/spg_hip.h"
 #include "spg_ecc.h"
-#include "spg_gemm.h"
+#include "spg_dense.h"
 #include "spg_narrow.h"
 #include <limits.h>
 #include <mutex>
@@ -36,23 +36,11 @@ bool gram_recorded(const void* slots) {
   return it != g_gram_filled.end() && it->second;
 }
 
-struct Layer {
-  int cin = 0, cout = 0;
-  bool bn = false;
+struct Layer : SpgDenseLayer {
   bool conv = false;            // rows = points (B*P) instead of superpoints (B)
-  const float *W = nullptr, *b = nullptr, *gamma = nullptr, *beta = nullptr;
-  float *rm = nullptr, *rv = nullptr;
-  float* y = nullptr;           // raw output (workspace or external)
-  long ldy = 0;
   float* Wpack = nullptr;       // conv layers, inference: weights in MFMA operand order (spg_convstack.hip)
   void *Wb_f = nullptr, *Wb_t = nullptr;   // conv layers with whole reduction chunks: bf16 hi/lo copies of W for the opt-in bf16 MFMA
                                 // modes (spg_launch_split_weights): forward orientation [2][cout][cin], transposed [2][cin][cout]
-  float* Wpad = nullptr;        // FC layers whose input width is not a multiple of 4: zero-padded copy of W
-  long ldw = 0;                 // leading dimension of the weight actually fed to the kernels
-  float *mean = nullptr, *rstd = nullptr, *s = nullptr, *t = nullptr;   // BN batch constants
-  unsigned long long* slots = nullptr;      // train mode: fixed-point statistics slots of this layer (SpgBnFold, spg_gemm.h)
-  unsigned long long* slots_bwd = nullptr;  // the same for the backward sums (sum dz, sum dz * xhat)
-  float *dW = nullptr, *db = nullptr, *dgamma = nullptr, *dbeta = nullptr;
 };
 
 struct Segment {           // convs (BN+ReLU each) -> max-pool (+concat) -> fcs (BN+ReLU each, last one plain)
@@ -84,19 +72,6 @@ struct Plan {
   size_t bytes = 0;
 };
 
-struct Carver {
-  char* base;
-  size_t off = 0;
-  explicit Carver(void* b) : base((char*)b) {}
-  template <typename T>
-  T* take(size_t n) {
-    off = (off + 255) & ~(size_t)255;
-    T* p = base ? (T*)(base + off) : nullptr;
-    off += n * sizeof(T);
-    return p;
-  }
-};
-
 int num_layers(const spg_pointnet_cfg& c) {
   return (c.nfeat_stn > 0 ? c.n_stn_conv + c.n_stn_fc + 1 : 0) + c.n_conv + c.n_fc;
 }
@@ -116,7 +91,7 @@ int make_plan(const spg_pointnet_cfg* cfg, int B, int training, void* ws, const 
   pl.has_stn = c.nfeat_stn > 0;
   pl.L.clear();
   auto add = [&](int cin, int cout, bool bn, bool conv) {
-    Layer l; l.cin = cin; l.cout = cout; l.bn = bn; l.conv = conv;
+    Layer l; l.cin = cin; l.cout = cout; l.bn = bn; l.relu = bn; l.conv = conv;      // (every BatchNorm here is followed by a ReLU)
     pl.L.push_back(l);
     return (int)pl.L.size() - 1;
   };
@@ -132,17 +107,11 @@ int make_plan(const spg_pointnet_cfg* cfg, int B, int training, void* ws, const 
     pl.main.fcs.push_back(add(i ? c.fc[i - 1] : c.conv[c.n_conv - 1] + c.nfeat_global, c.fc[i], i < c.n_fc - 1, false));
   pl.main.nextra = c.nfeat_global;
 
-  Carver cv(ws);
+  SpgCarver cv(ws);
   int cmax = 4;
   for (size_t i = 0; i < pl.L.size(); ++i) {
     Layer& l = pl.L[i];
-    if (params) {
-      const void* const* g = params + 6 * i;
-      l.W = (const float*)g[0]; l.b = (const float*)g[1]; l.gamma = (const float*)g[2]; l.beta = (const float*)g[3];
-      l.rm = (float*)g[4]; l.rv = (float*)g[5];
-      SPG_CHECK_ARG(l.W != nullptr, "missing layer weight");
-      SPG_CHECK_ARG(!l.bn || (l.rm != nullptr && l.rv != nullptr), "missing BatchNorm running statistics");
-    }
+    if (params) SPG_TRY(spg_dense_bind_params(l, params + 6 * i));
     cmax = l.cout > cmax ? l.cout : cmax;
     if (l.bn) {
       l.mean = cv.take<float>(l.cout); l.rstd = cv.take<float>(l.cout);
@@ -212,19 +181,9 @@ int make_plan(const spg_pointnet_cfg* cfg, int B, int training, void* ws, const 
   return 0;
 }
 
-SpgOperand op_affine(const Layer& prod, const float* X, long ld, int n_affine) {
-  SpgOperand o; memset(&o, 0, sizeof(o));
-  o.mode = SPG_PRO_AFFINE; o.X = X; o.ld = ld; o.c0 = prod.s; o.c1 = prod.t; o.relu = 1; o.n_affine = n_affine;
-  return o;
-}
 SpgOperand op_cloud(const Plan& pl, const float* clouds, const float* stnT) {
   SpgOperand o; memset(&o, 0, sizeof(o));
   o.mode = SPG_PRO_CLOUD; o.X = clouds; o.Ctot = pl.cfg.nfeat; o.P = pl.P; o.stnT = stnT;
-  return o;
-}
-SpgOperand op_ident(const float* X, long ld) {
-  SpgOperand o; memset(&o, 0, sizeof(o));
-  o.mode = SPG_PRO_IDENT; o.X = X; o.ld = ld;
   return o;
 }
 
@@ -233,32 +192,23 @@ SpgOperand input_operand(const Plan& pl, const Segment& sg, bool is_fc, size_t k
   if (!is_fc) {
     if (k == 0) return op_cloud(pl, clouds, stnT);
     const Layer& p = pl.L[sg.convs[k - 1]];
-    return op_affine(p, p.y, p.ldy, p.cout);
+    return spg_op_affine(p, p.y, p.ldy);
   }
   if (k == 0) {
     const Layer& p = pl.L[sg.convs.back()];
-    return op_affine(p, sg.pooled, sg.ldpool, p.cout);
+    return spg_op_affine(p, sg.pooled, sg.ldpool);
   }
   const Layer& p = pl.L[sg.fcs[k - 1]];
-  return op_affine(p, p.y, p.ldy, p.cout);
+  return spg_op_affine(p, p.y, p.ldy);
 }
 
-// the statistics of `prod` (rows = `count`) finished in the prologue of the launch that consumes its output
-SpgBnFold fold_of(const Plan& pl, const Layer& prod, long count, int update_times) {
-  SpgBnFold f; memset(&f, 0, sizeof(f));
-  if (!pl.fold || !prod.bn) return f;
-  f.slots = prod.slots; f.C = prod.cout; f.update_times = update_times; f.momentum = pl.cfg.bn_momentum; f.eps = pl.cfg.bn_eps;
-  f.count = (double)count; f.gamma = prod.gamma; f.beta = prod.beta; f.rm = prod.rm; f.rv = prod.rv;
-  f.mean = prod.mean; f.rstd = prod.rstd; f.s = prod.s; f.t = prod.t;
-  return f;
-}
-
-int bn_stats(const Plan& pl, Layer& l, int nparts, long M, int update_times, hipStream_t st) {
-  if (pl.training && pl.fold) return 0;      // finished by the consumer (fold_of)
-  if (pl.training)
-    return spg_launch_bn_finalize(pl.stat, pl.stat_cnt, nparts, M, l.cout, l.gamma, l.beta, l.rm, l.rv,
-                                  pl.cfg.bn_momentum, pl.cfg.bn_eps, update_times, l.mean, l.rstd, l.s, l.t, pl.fin, st);
-  return 0;     // eval mode: all layers were handled by one spg_launch_bn_eval_batch at the start of the forward
+// the BatchNorm side of one pass (spg_dense.h)
+SpgDenseBn bn_of(const Plan& pl, int update_times, float* stat, double* fin, float* consts) {
+  SpgDenseBn bn;
+  bn.training = pl.training; bn.fold = pl.fold; bn.update_times = update_times;
+  bn.momentum = pl.cfg.bn_momentum; bn.eps = pl.cfg.bn_eps;
+  bn.stat = stat; bn.stat_cnt = pl.stat_cnt; bn.fin = fin; bn.consts = consts;
+  return bn;
 }
 
 // inference: the whole convolution stack + max-pool of a segment in one kernel (spg_convstack.hip), when its shape allows
@@ -315,7 +265,7 @@ int forward_segment(Plan& pl, Segment& sg, const float* clouds, const float* stn
     const bool last = k + 1 == sg.convs.size();
     SpgGemmParams g; memset(&g, 0, sizeof(g));
     g.a = input_operand(pl, sg, false, k, clouds, stnT);
-    if (k > 0) g.fold = fold_of(pl, pl.L[sg.convs[k - 1]], pl.M, update_times);
+    if (k > 0 && pl.fold) g.fold = spg_fold_of(pl.L[sg.convs[k - 1]], pl.M, update_times, pl.cfg.bn_momentum, pl.cfg.bn_eps);
     g.W = l.W; g.ldw = l.cin; g.bias = l.b; g.M = (int)pl.M; g.N = l.cout; g.K = l.cin;
     g.rows_per_tile = pl.P; g.epi = SPG_EPI_FWD; g.Y = l.y; g.ldy = l.ldy;
     if (l.Wb_f != nullptr) { g.Wb = l.Wb_f; g.ldwb = spg_split_ld(l.cin); g.wb_part_bytes = (long)l.cout * g.ldwb * 2; }
@@ -328,17 +278,15 @@ int forward_segment(Plan& pl, Segment& sg, const float* clouds, const float* stn
       g.pool_extra = sg.extra; g.pool_nextra = sg.nextra;
     }
     SPG_TRY(spg_launch_gemm(g, st, &nparts));
-    SPG_TRY(bn_stats(pl, l, nparts, pl.M, update_times, st));
+    if (pl.training && !pl.fold)      // (eval mode: one spg_launch_bn_eval_batch at the start of the forward)
+      SPG_TRY(spg_launch_bn_finalize(pl.stat, pl.stat_cnt, nparts, pl.M, l.cout, l.gamma, l.beta, l.rm, l.rv,
+                                     pl.cfg.bn_momentum, pl.cfg.bn_eps, update_times, l.mean, l.rstd, l.s, l.t, pl.fin, st));
   }
   // every FC layer is a few-row launch: issued through a group scope (a group of one, or of two with the weight padding below),
   // so that a rider chain of the caller -- the filter network's forward -- can leave with it (spg_gemm.h)
   SpgGroupScope grp(st);
   for (size_t k = 0; k < sg.fcs.size(); ++k) {
     Layer& l = pl.L[sg.fcs[k]];
-    SpgGemmParams g; memset(&g, 0, sizeof(g));
-    g.a = input_operand(pl, sg, true, k, clouds, stnT);
-    // the producer's statistics: the last convolution (over all points) for the first fc layer, else the previous fc layer
-    g.fold = k == 0 ? fold_of(pl, pl.L[sg.convs.back()], pl.M, update_times) : fold_of(pl, pl.L[sg.fcs[k - 1]], pl.B, update_times);
     // zero-padded weight copies (input widths that are no multiples of 4: 256 pooled channels + the diameter): they depend on
     // the weights only -- all of them leave with the FIRST few-row launch of the forward that does not need one itself
     if (!pl.pads_done) {
@@ -352,17 +300,10 @@ int forward_segment(Plan& pl, Segment& sg, const float* clouds, const float* stn
       }
       pl.pads_done = true;
     }
-    g.W = l.Wpad ? l.Wpad : l.W; g.ldw = l.ldw; g.bias = l.b; g.M = pl.B; g.N = l.cout; g.K = l.cin;
-    g.rows_per_tile = SPG_FC_ROWS; g.epi = SPG_EPI_FWD; g.Y = l.y; g.ldy = l.ldy;
-    g.stat = (pl.training && l.bn) ? pl.stat : nullptr; g.stat_cnt = pl.stat_cnt;
-    if (pl.fold && l.bn) { g.stat = nullptr; g.stat_slots = l.slots; }
-    int nparts = 0;
-    {
-      SpgGroupBypass direct(l.bn && pl.training && !pl.fold);      // a finalize launch follows: the GEMM must not wait in the group
-      SPG_TRY(spg_launch_gemm(g, st, &nparts));
-    }
-    SPG_TRY(grp.flush());
-    if (l.bn) SPG_TRY(bn_stats(pl, l, nparts, pl.B, update_times, st));
+    // the producer's statistics: the last convolution (over all points) for the first fc layer, else the previous fc layer
+    const Layer& prod = k == 0 ? pl.L[sg.convs.back()] : pl.L[sg.fcs[k - 1]];
+    SPG_TRY(spg_dense_forward(l, &prod, input_operand(pl, sg, true, k, clouds, stnT), pl.B, k == 0 ? pl.M : (long)pl.B,
+                              bn_of(pl, update_times, pl.stat, pl.fin, nullptr), &grp, st));
   }
   return 0;
 }
@@ -383,7 +324,7 @@ struct BwdScratch {
 };
 
 void carve_bwd(const Plan& pl, void* ws, BwdScratch& s) {
-  Carver cv(ws);
+  SpgCarver cv(ws);
   int cconv = 4, cfc = 4, cmax = 4;
   size_t wmax = 16, workmax = 16;
   for (const Layer& l : pl.L) {
@@ -392,8 +333,7 @@ void carve_bwd(const Plan& pl, void* ws, BwdScratch& s) {
     cmax = l.cout > cmax ? l.cout : cmax; cmax = l.cin > cmax ? l.cin : cmax;
     wmax = (size_t)l.cin * l.cout > wmax ? (size_t)l.cin * l.cout : wmax;
     // every layer gets its own slice of the reduction arena (partials stay alive until the single batched reduce)
-    workmax += ((spg_wgrad_workspace_floats(l.conv ? pl.M : pl.B, l.cout, l.cin) + 63) & ~(size_t)63) + 64 * (size_t)l.cout + 128 +
-               ((spg_wgrad_colsum_floats(l.conv ? pl.M : pl.B, l.cout, l.cin) + 63) & ~(size_t)63);
+    workmax += spg_queue_layer_floats(l.conv ? pl.M : pl.B, l.cout, l.cin);
     // (the one-pass backward of a segment's first convolution writes one partial per wave, spg_narrow.h)
     if (l.conv && l.cin <= SPG_GRAM_MAXF) workmax += ((size_t)spg_first_conv_bwd_partials(pl.B) * l.cout * l.cin + 63) & ~(size_t)63;
   }
@@ -408,31 +348,8 @@ void carve_bwd(const Plan& pl, void* ws, BwdScratch& s) {
   s.bytes = cv.off + 256;
 }
 
-SpgOperand op_bnbwd(const float* dz, const float* y, long ld, const float* consts, int C) {
-  SpgOperand o; memset(&o, 0, sizeof(o));
-  o.mode = SPG_PRO_BNBWD; o.X = dz; o.X2 = y; o.ld = ld;
-  o.c0 = consts; o.c1 = consts + C; o.c2 = consts + 2 * C; o.c3 = consts + 3 * C;
-  return o;
-}
-
-int zero_async(float* p, size_t n, hipStream_t st) {
-  if (p == nullptr || n == 0) return 0;
-  hipError_t e = hipMemsetAsync(p, 0, n * sizeof(float), st);
-  if (e != hipSuccess) { spg_set_error("hipMemsetAsync: %s", hipGetErrorString(e)); return (int)e; }
-  return 0;
-}
-
 // Backward of one segment.  `cur` is the gradient wrt the raw output of the segment's last fc layer
 // (IDENT operand).  If want_dxy, the gradient wrt the first two input channels of conv 0 is left in s.dxy.
-// the BatchNorm-backward sums of `prod` (rows = count), to be finished by the next weight-gradient launch (spg_gemm.h)
-SpgBnFoldBwd fold_bwd_of(const Plan& pl, const Layer& prod, long count, float* consts) {
-  SpgBnFoldBwd f; memset(&f, 0, sizeof(f));
-  f.slots = prod.slots_bwd; f.C = prod.cout; f.count = (double)count; f.s = prod.s; f.mean = prod.mean; f.rstd = prod.rstd;
-  f.consts = consts; f.dgamma = prod.dgamma; f.dbeta = prod.dbeta;
-  if (spg_slot_sync_active()) f.grad_mul = 1.0 / (double)spg_slot_sync_world();
-  return f;
-}
-
 // dT_out / dT_done: with want_dxy, the one-pass backward of the first convolution (spg_narrow.h) writes the gradient of the 2 x 2
 // transforms [B, 4] itself and sets *dT_done; otherwise s.dxy holds the gradient wrt the transformed xy for spg_launch_stn_dT
 int backward_segment(Plan& pl, Segment& sg, BwdScratch& s, SpgReduceQueue& rq, SpgOperand cur, const float* clouds,
@@ -442,8 +359,7 @@ int backward_segment(Plan& pl, Segment& sg, BwdScratch& s, SpgReduceQueue& rq, S
   SpgBnFoldBwd pending; memset(&pending, 0, sizeof(pending));     // set by a data-gradient launch, consumed by the next weight gradient
   // ---- fc head ----
   // A layer's weight gradient and its data gradient depend on the same inputs and not on each other: both few-row launches
-  // leave as ONE grouped launch (spg_gemm.h) -- three launches per head instead of six.  The data gradient then finishes the
-  // BatchNorm-backward constants of its operand itself (fold_bwd), since the weight gradient is no longer ordered before it.
+  // leave as ONE grouped launch (spg_gemm.h) -- three launches per head instead of six (spg_dense_backward).
   float* fz[2] = {s.fzA, s.fzB};
   int flip = 0;
   {
@@ -454,45 +370,23 @@ int backward_segment(Plan& pl, Segment& sg, BwdScratch& s, SpgReduceQueue& rq, S
   for (int k = (int)sg.fcs.size() - 1; k >= 0; --k) {
     if (ride_reduce) SPG_TRY(spg_reduce_ride(rq, st));      // (a slice per group; before this layer queues its own partials)
     Layer& l = pl.L[sg.fcs[k]];
-    SpgWgradParams w; memset(&w, 0, sizeof(w));
-    w.a = cur; w.b = input_operand(pl, sg, true, k, clouds, stnT); w.M = B; w.N = l.cout; w.K = l.cin;
-    w.fold = pending;
-    const SpgBnFoldBwd fold_k = pending;
-    memset(&pending, 0, sizeof(pending));
-    // a bias without BatchNorm behind it: its gradient (column sums of `cur`, an IDENT operand here) rides along with the
-    // weight gradient; a bias in front of train-mode BatchNorm has zero gradient
-    const bool bias_rides = l.db != nullptr && !l.bn && cur.mode == SPG_PRO_IDENT;
-    SPG_TRY(spg_queue_wgrad(rq, w, l.dW, st, bias_rides ? l.db : nullptr));
-    if (l.db && !bias_rides) {
-      if (l.bn) SPG_TRY(spg_group_zero(l.db, l.cout, st));
-      else SPG_TRY(spg_queue_colsum(rq, cur.X, cur.ld, B, l.cout, l.db, st));
-    }
-    // data gradient -> producer of this layer's input
+    // data gradient -> producer of this layer's input; the first fc layer reads the pooled rows of the last convolution, whose
+    // statistics run over all points
     const bool first = k == 0;
     Layer& prod = first ? pl.L[sg.convs.back()] : pl.L[sg.fcs[k - 1]];
     float* out = fz[flip]; flip ^= 1;
-    SpgGemmParams g; memset(&g, 0, sizeof(g));
-    g.a = cur; g.W = l.Wpad ? l.Wpad : l.W; g.ldw = l.ldw; g.w_red = 1;   // dz_prev = dy @ W, W read untransposed
-    g.M = B; g.N = l.cin; g.K = l.cout; g.rows_per_tile = SPG_FC_ROWS;
-    g.epi = SPG_EPI_BWD; g.Y = out; g.ldy = first ? sg.ldpool : l.cin;
-    g.Yp = first ? sg.pooled : prod.y; g.ldyp = first ? sg.ldpool : prod.ldy;
-    g.ms = prod.s; g.mt = prod.t; g.mask_relu = 1; g.n_mask = prod.cout;
-    g.mmean = prod.mean; g.mrstd = prod.rstd; g.stat = s.stat;
-    if (pl.fold) { g.stat = nullptr; g.stat_slots = prod.slots_bwd; g.stat_rows = first ? pl.M : (long)B; }
-    if (grp.active()) g.fold_bwd = fold_k;
-    int nparts = 0;
-    SPG_TRY(spg_launch_gemm(g, st, &nparts));
-    SPG_TRY(grp.flush());      // {weight gradient, bias column sums, data gradient} of this layer
-    // the statistics cover the producer's channels only (N = l.cin may be larger by nextra for the pooled input)
+    SpgDenseDgrad d;
+    d.prod = &prod; d.out = out; d.ldout = first ? sg.ldpool : l.cin;
+    d.Yp = first ? sg.pooled : prod.y; d.ldyp = first ? sg.ldpool : prod.ldy;
+    d.count = d.stat_rows = first ? pl.M : (long)B;
+    d.folds = grp.active();      // (separate launches: the weight gradient runs first and finishes the constants)
+    SPG_TRY(spg_dense_backward(rq, l, cur, input_operand(pl, sg, true, k, clouds, stnT), B, d, bn_of(pl, 1, s.stat, s.fin, s.consts),
+                               pending, &grp, st));      // flushed: {weight gradient, bias column sums, data gradient} of this layer
     const int C = prod.cout;
     if (first && s.grad_global != nullptr && sg.nextra > 0)     // columns >= C pass through: gradient wrt the global features
       SPG_TRY(spg_launch_copy2d(out + C, sg.ldpool, s.grad_global, sg.nextra, B, sg.nextra, st));
-    if (pl.fold) pending = fold_bwd_of(pl, prod, first ? pl.M : (long)B, s.consts);      // finished by the next weight gradient
-    else
-    SPG_TRY(spg_launch_bn_bwd_finalize(s.stat, nparts, l.cin, first ? pl.M : (long)B, C, prod.s, prod.mean,
-                                       prod.rstd, s.consts, prod.dgamma, prod.dbeta, s.fin, st));
     if (!first) {
-      cur = op_bnbwd(out, prod.y, prod.ldy, s.consts, C);
+      cur = spg_op_bnbwd(out, prod.y, prod.ldy, s.consts, C);
     } else {
       memset(&cur, 0, sizeof(cur));
       cur.mode = SPG_PRO_POOLBWD; cur.X = out; cur.ldg = (int)sg.ldpool; cur.aidx = sg.aidx; cur.P = pl.P;
@@ -519,10 +413,10 @@ int backward_segment(Plan& pl, Segment& sg, BwdScratch& s, SpgReduceQueue& rq, S
       const SpgOperand xin = input_operand(pl, sg, false, k, clouds, stnT);
       if (spg_bwdpair_supported(g, xin)) {
         SPG_TRY(spg_queue_bwdpair(rq, g, xin, l.dW, st));
-        if (l.db) SPG_TRY(zero_async(l.db, l.cout, st));
+        if (l.db) SPG_TRY(spg_zero_bytes_async(l.db, sizeof(float) * l.cout, st));
         flip ^= 1;
-        pending = fold_bwd_of(pl, prod, pl.M, s.consts);      // (the launch consumed this layer's; these are the producer's)
-        cur = op_bnbwd(out, prod.y, prod.ldy, s.consts, prod.cout);
+        pending = spg_fold_bwd_of(prod, pl.M, s.consts);      // (the launch consumed this layer's; these are the producer's)
+        cur = spg_op_bnbwd(out, prod.y, prod.ldy, s.consts, prod.cout);
         continue;
       }
     }
@@ -538,7 +432,7 @@ int backward_segment(Plan& pl, Segment& sg, BwdScratch& s, SpgReduceQueue& rq, S
       fp.dT = want_dxy ? dT_out : nullptr;
       SPG_TRY(spg_queue_partials(rq, spg_first_conv_bwd_partials(pl.B), l.cout * l.cin, l.dW, &fp.partial, st));
       SPG_TRY(spg_launch_first_conv_bwd(fp, st));
-      if (l.db) SPG_TRY(zero_async(l.db, l.cout, st));
+      if (l.db) SPG_TRY(spg_zero_bytes_async(l.db, sizeof(float) * l.cout, st));
       if (want_dxy && dT_done != nullptr) *dT_done = true;
       continue;
     }
@@ -547,7 +441,7 @@ int backward_segment(Plan& pl, Segment& sg, BwdScratch& s, SpgReduceQueue& rq, S
     w.fold = pending; memset(&pending, 0, sizeof(pending));
     w.allow_lowp = 1;      // the opt-in precision modes act on the PointNet convolutions only
     SPG_TRY(spg_queue_wgrad(rq, w, l.dW, st));
-    if (l.db) SPG_TRY(zero_async(l.db, l.cout, st));
+    if (l.db) SPG_TRY(spg_zero_bytes_async(l.db, sizeof(float) * l.cout, st));
     if (k > 0) {
       Layer& prod = pl.L[sg.convs[k - 1]];
       float* out = dz[flip]; flip ^= 1;
@@ -562,11 +456,11 @@ int backward_segment(Plan& pl, Segment& sg, BwdScratch& s, SpgReduceQueue& rq, S
       if (foldk) { g.stat = nullptr; g.stat_slots = prod.slots_bwd; }
       int nparts = 0;
       SPG_TRY(spg_launch_gemm(g, st, &nparts));
-      if (foldk) pending = fold_bwd_of(pl, prod, pl.M, s.consts);
+      if (foldk) pending = spg_fold_bwd_of(prod, pl.M, s.consts);
       else
       SPG_TRY(spg_launch_bn_bwd_finalize(s.stat, nparts, l.cin, pl.M, prod.cout, prod.s, prod.mean, prod.rstd, s.consts,
                                          prod.dgamma, prod.dbeta, s.fin, st));
-      cur = op_bnbwd(out, prod.y, prod.ldy, s.consts, prod.cout);
+      cur = spg_op_bnbwd(out, prod.y, prod.ldy, s.consts, prod.cout);
     } else if (want_dxy) {
       // gradient wrt the transformed xy only (learning/pointnet.py:123-124): 2 output columns
       SpgGemmParams g; memset(&g, 0, sizeof(g));
@@ -577,13 +471,6 @@ int backward_segment(Plan& pl, Segment& sg, BwdScratch& s, SpgReduceQueue& rq, S
     }
   }
   return 0;
-}
-
-void bind_grads(Plan& pl, void* const* grads) {
-  for (size_t i = 0; i < pl.L.size(); ++i) {
-    void* const* g = grads + 6 * i;
-    pl.L[i].dW = (float*)g[0]; pl.L[i].db = (float*)g[1]; pl.L[i].dgamma = (float*)g[2]; pl.L[i].dbeta = (float*)g[3];
-  }
 }
 
 }  // namespace
@@ -637,11 +524,10 @@ extern "C" int spg_pointnet_forward_ext(const spg_pointnet_cfg* cfg, int B, cons
       }
     SPG_TRY(spg_launch_split_weights(sb, st));
   }
-  // train mode: BatchNorm statistics travel as fixed-point slots from each producer GEMM to its consumer (spg_gemm.h) -- no
-  // finalize launches; not with synchronised BatchNorm (the ranks' all-reduce sits between producer and consumer)
-  // (every tile contributes at most 4 wave partials per channel: far below the slots' capacity up to ~500 k superpoints)
-  pl.fold = pl.training && !spg_sync_bn_active() && !spg_tune_get(SPG_TUNE_NO_BN_FOLD) && 4L * B * spg_slot_sync_world() <= SPG_FOLD_MAX_CONTRIBUTIONS;
-  SPG_CHECK_ARG(!(pl.training && spg_slot_sync_active()) || pl.fold, "slot-synchronised BatchNorm needs the statistics slots (spg_tune key 10 off, batch within the slots' capacity)");
+  // train mode: the BatchNorm statistics travel as slots from each producer GEMM to its consumer; every tile
+  // contributes at most 4 wave partials per channel: within the slots' capacity up to ~500 k superpoints
+  pl.fold = pl.training && spg_bn_fold_allowed(4L * B);
+  SPG_TRY(spg_bn_slot_sync_check(pl.training, pl.fold, "slot-synchronised BatchNorm needs the statistics slots (spg_tune key 10 off, batch within the slots' capacity)"));
   if (pl.training && !g_slots_clean) {      // always in train mode: the backward decides about its own slots independently (they are cleared here too)
     hipError_t me = hipMemsetAsync(pl.slots_all, 0, pl.slots_words * sizeof(unsigned long long), st);
     if (me != hipSuccess) { spg_set_error("hipMemsetAsync: %s", hipGetErrorString(me)); return (int)me; }
@@ -706,8 +592,8 @@ extern "C" int spg_pointnet_backward_ext(const spg_pointnet_cfg* cfg, int B, con
   // the forward wrote the last fc output to `emb`; it is not needed by the backward, so pass a dummy
   SPG_TRY(make_plan(cfg, B, 1, workspace, params, (float*)grad_emb /*unused as y*/, pl));
   pl.main.extra = clouds_global;
-  pl.fold = !spg_sync_bn_active() && !spg_tune_get(SPG_TUNE_NO_BN_FOLD) && 4L * B * spg_slot_sync_world() <= SPG_FOLD_MAX_CONTRIBUTIONS;
-  bind_grads(pl, grads);
+  pl.fold = spg_bn_fold_allowed(4L * B);
+  for (size_t i = 0; i < pl.L.size(); ++i) spg_dense_bind_grads(pl.L[i], grads + 6 * i);
   BwdScratch s;
   carve_bwd(pl, bwd_workspace, s);
   const float* stnT = pl.has_stn ? pl.L[pl.stn.fcs.back()].y : ext_transform;
@@ -717,13 +603,13 @@ extern "C" int spg_pointnet_backward_ext(const spg_pointnet_cfg* cfg, int B, con
   s.grad_global = grad_global;
   bool dT_done = false;
   float* dT_target = grad_transform != nullptr ? grad_transform : (pl.has_stn ? s.dT : nullptr);
-  SPG_TRY(backward_segment(pl, pl.main, s, rq, op_ident(grad_emb, cout), clouds, stnT, pl.has_stn || grad_transform != nullptr, st, false,
+  SPG_TRY(backward_segment(pl, pl.main, s, rq, spg_op_ident(grad_emb, cout), clouds, stnT, pl.has_stn || grad_transform != nullptr, st, false,
                            dT_target, &dT_done));
   if (grad_transform != nullptr && !dT_done)      // gradient wrt the external 2x2 transforms (learning/pointnet.py:196-198)
     SPG_TRY(spg_launch_stn_dT(clouds, pl.cfg.nfeat, pl.P, B, s.dxy, 2, grad_transform, st));
   if (pl.has_stn) {
     if (!dT_done) SPG_TRY(spg_launch_stn_dT(clouds, pl.cfg.nfeat, pl.P, B, s.dxy, 2, s.dT, st));
-    SPG_TRY(backward_segment(pl, pl.stn, s, rq, op_ident(s.dT, 4), clouds, nullptr, false, st, true));
+    SPG_TRY(backward_segment(pl, pl.stn, s, rq, spg_op_ident(s.dT, 4), clouds, nullptr, false, st, true));
   }
   if (g_slots_clear_at_end && pl.slots_all != nullptr && pl.slots_words > 0) {
     SPG_CHECK_ARG(2 * pl.slots_words < (size_t)INT_MAX, "statistics slots too large for one reduction job");
