@@ -187,16 +187,12 @@ __global__ __launch_bounds__(EL_BLOCK) void edge_fwd_kernel(FwdArgs a) {
     }
   }
   if (DO_LOSS) {
-    // fixed tree: xor-shuffles inside the wavefront, then the four wavefronts in order
-    __shared__ double s1[EL_BLOCK / 64], s2[EL_BLOCK / 64];
-    for (int o = 32; o >= 1; o >>= 1) { t1 += __shfl_xor(t1, o, 64); t2 += __shfl_xor(t2, o, 64); }
-    if ((threadIdx.x & 63) == 0) { s1[threadIdx.x >> 6] = t1; s2[threadIdx.x >> 6] = t2; }
-    __syncthreads();
+    __shared__ double lds[PART_WAVES][2];
+    double t[2] = {t1, t2};
+    block_reduce<PartAll<PART_SUM>>(t, lds);      // the fixed order of spg_part.h
     if (threadIdx.x == 0) {
-      double r1 = s1[0], r2 = s2[0];
-      for (int i = 1; i < EL_BLOCK / 64; ++i) { r1 += s1[i]; r2 += s2[i]; }
-      a.partials[2 * (long)blockIdx.x] = r1;
-      a.partials[2 * (long)blockIdx.x + 1] = r2;
+      a.partials[2 * (long)blockIdx.x] = t[0];
+      a.partials[2 * (long)blockIdx.x + 1] = t[1];
     }
   }
 }

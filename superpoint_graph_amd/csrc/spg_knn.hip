@@ -97,18 +97,7 @@ __device__ __forceinline__ double knn_d2(double qx, double qy, double qz, float 
 // build
 // -------------------------------------------------------------------------------------------------------------------
 __global__ void minmax_kernel(const float* __restrict__ xyz, long n, KnnParams* __restrict__ p) {
-  float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-  bool bad = false;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
-    for (int d = 0; d < 3; ++d) {
-      const float v = xyz[3 * i + d];
-      bad |= !isfinite(v);
-      lo[d] = fminf(lo[d], v); hi[d] = fmaxf(hi[d], v);
-    }
-  for (int d = 0; d < 3; ++d) {
-    for (int o = 32; o >= 1; o >>= 1) { lo[d] = fminf(lo[d], __shfl_xor(lo[d], o, 64)); hi[d] = fmaxf(hi[d], __shfl_xor(hi[d], o, 64)); }
-    if ((threadIdx.x & 63) == 0) { atomicMin(&p->mm[d], ordered_bits(lo[d])); atomicMax(&p->mm[3 + d], ordered_bits(hi[d])); }
-  }
+  const bool bad = axis_minmax(xyz, n, p->mm);
   if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&p->flag, 1u);
 }
 

@@ -2,12 +2,9 @@
 // (learning/s3dis_dataset.py:93-162, sema3d_dataset.py:85-135, vkitti_dataset.py:83-130, custom_dataset.py:67-107), restated
 // (tests/parsed_restatement.py is the same text in numpy).  Three entry points:
 //
-// spg_parsed_stats   the scene statistics by fixed-order reductions: every pass is a grid of min(ceil(n / 256), 1024) workgroups
-//                    with a grid stride -> a wave butterfly -> the four waves in order -> partials [blocks] -> ONE workgroup that
-//                    adds the partials in the same shape.  The grid depends on n alone, there is no atomic and no waiting between
-//                    workgroups: the same input gives the same bits.  Pass 0: min / max per axis in float32, the sums of x, y, z in
-//                    float64, the finite check.  Passes 1, 2 (S3DIS only): the sum of d = sqrt((x - cx)^2 + (y - cy)^2), then of
-//                    (d - mean d)^2, in float64 (numpy's two-pass std, ddof = 0).
+// spg_parsed_stats   the scene statistics by the fixed-order reduction of spg_part.h (the same input gives the same bits).  Pass 0:
+//                    min / max per axis in float32, the sums of x, y, z in float64, the finite check.  Passes 1, 2 (S3DIS only): the
+//                    sum of d = sqrt((x - cx)^2 + (y - cy)^2), then of (d - mean d)^2, in float64 (numpy's two-pass std, ddof = 0).
 // spg_parsed_rows    one pass: output row r -> its superpoint by bisection of the output offsets -> its source vertex through the
 //                    component list (and the trim table) -> the columns of the recipe, into LDS; the workgroup's PR_ROWS rows leave
 //                    as ONE contiguous span of 16-byte non-temporal stores (rows of 11 / 14 / 15 floats are not 16-byte aligned,
@@ -26,56 +23,13 @@
 
 namespace {
 
-constexpr int PR_BLOCK = 256;
-constexpr int PR_WAVES = PR_BLOCK / 64;
-constexpr int PR_MAX_BLOCKS = 1024;      // workgroups of a reduction pass (grid-stride beyond)
+constexpr int PR_BLOCK = PART_BLOCK;
 constexpr int PR_ROWS = PR_BLOCK;        // output rows per workgroup of the row pass: one per lane
 constexpr int PR_MAX_COLS = 15;
 constexpr int PR_MAX_CLASSES = 4096;     // the LDS histogram of the class count
 
 // stats_f32 [6]: min x, y, z, max x, y, z.  stats_f64 [5]: mean x, y, z, mean d, std d.
-__device__ __forceinline__ bool finite_f32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 __device__ __forceinline__ float div_rn_f32(float a, float b) { return (float)((double)a / (double)b); }
-
-template <int OP>      // 0 min, 1 max, 2 sum
-__device__ __forceinline__ double combine(double a, double b) { return OP == 0 ? fmin(a, b) : OP == 1 ? fmax(a, b) : a + b; }
-
-// the workgroup's value of `v` in lane 0 of wave 0's view: butterfly inside the wave, then the waves in order.  (The butterfly gives
-// every lane the same bits: a + b and b + a are one value.)  Every thread returns the result.
-template <int OP>
-__device__ __forceinline__ double block_reduce(double v, double* lds) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = combine<OP>(v, __shfl_xor(v, off, 64));
-  __syncthreads();                                   // (the previous use of lds is over)
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double r = lds[0];
-#pragma unroll
-  for (int w = 1; w < PR_WAVES; ++w) r = combine<OP>(r, lds[w]);
-  return r;
-}
-
-// PASS 0: v[0..2] min, v[3..5] max, v[6..8] sums of x, y, z.  PASS 1: v[0] = sum d.  PASS 2: v[0] = sum (d - mean d)^2.
-template <int PASS>
-__device__ __forceinline__ void reduce_and_store(double (&v)[9], double* lds, double* out) {
-  if (PASS == 0) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      v[c] = block_reduce<0>(v[c], lds);
-      v[3 + c] = block_reduce<1>(v[3 + c], lds);
-      v[6 + c] = block_reduce<2>(v[6 + c], lds);
-    }
-    if (threadIdx.x < 9) {
-      double r = v[0];
-#pragma unroll
-      for (int c = 1; c < 9; ++c) r = threadIdx.x == c ? v[c] : r;
-      out[threadIdx.x] = r;
-    }
-  } else {
-    v[0] = block_reduce<2>(v[0], lds);
-    if (threadIdx.x == 0) out[0] = v[0];
-  }
-}
 
 __device__ __forceinline__ double centre_distance(const float* __restrict__ xyz, long i, double cx, double cy) {
 #pragma clang fp contract(off)
@@ -84,80 +38,55 @@ __device__ __forceinline__ double centre_distance(const float* __restrict__ xyz,
   return sqrt(xx + yy);
 }
 
-template <int PASS>
-__global__ __launch_bounds__(PR_BLOCK) void stats_partial_kernel(const float* __restrict__ xyz, long n, const double* __restrict__ stats_f64,
-                                                                 double* __restrict__ partials, int32_t* __restrict__ err) {
-#pragma clang fp contract(off)
-  __shared__ double lds[PR_WAVES];
-  double v[9] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY, 0.0, 0.0, 0.0};
-  if (PASS != 0) v[0] = 0.0;
-  int bad = 0;
-  const double cx = PASS != 0 ? stats_f64[0] : 0.0, cy = PASS != 0 ? stats_f64[1] : 0.0, dmean = PASS == 2 ? stats_f64[3] : 0.0;
-  for (long i = (long)blockIdx.x * PR_BLOCK + threadIdx.x; i < n; i += (long)gridDim.x * PR_BLOCK) {
-    if (PASS == 0) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const float x = xyz[3 * i + c];
-        bad |= !finite_f32(x);
-        v[c] = fmin(v[c], (double)x);
-        v[3 + c] = fmax(v[3 + c], (double)x);
-        v[6 + c] += (double)x;
-      }
-    } else {
-      const double d = centre_distance(xyz, i, cx, cy);
-      if (PASS == 1) v[0] += d;
-      else { const double t = d - dmean; v[0] += t * t; }
-    }
-  }
-  if (PASS == 0) {
-    bad = __syncthreads_or(bad);
-    if (threadIdx.x == 0 && bad) atomicOr(err, 1);
-  }
-  reduce_and_store<PASS>(v, lds, partials + (long)blockIdx.x * 9);
-}
-
-// one workgroup: the partials in the same shape, then the statistics of the pass
-template <int PASS>
-__global__ __launch_bounds__(PR_BLOCK) void stats_final_kernel(const double* __restrict__ partials, int nb, long n, float* __restrict__ stats_f32,
-                                                               double* __restrict__ stats_f64, float* __restrict__ centroid) {
-#pragma clang fp contract(off)
-  __shared__ double lds[PR_WAVES];
-  __shared__ double res[9];
-  double v[9] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY, 0.0, 0.0, 0.0};
-  if (PASS != 0) v[0] = 0.0;
-  for (int b = threadIdx.x; b < nb; b += PR_BLOCK) {
-    const double* p = partials + (long)b * 9;
-    if (PASS == 0) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        v[c] = fmin(v[c], p[c]);
-        v[3 + c] = fmax(v[3 + c], p[3 + c]);
-        v[6 + c] += p[6 + c];
-      }
-    } else {
-      v[0] += p[0];
-    }
-  }
-  reduce_and_store<PASS>(v, lds, res);
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  const double dn = (double)n;
-  if (PASS == 0) {
-#pragma unroll
-    for (int c = 0; c < 6; ++c) stats_f32[c] = (float)res[c];        // (exact: the minimum of float32 values)
+// The passes (spg_part.h) of the scene statistics.  Pass 0: v[0..2] min, v[3..5] max, v[6..8] sums of x, y, z, and the finite check.
+struct StatsPass0 {
+  typedef double T;
+  static constexpr int K = 9;
+  static constexpr int op(int c) { return c < 3 ? PART_MIN : c < 6 ? PART_MAX : PART_SUM; }
+  float* stats_f32;
+  double* stats_f64;
+  float* centroid;
+  __device__ void point(const float* __restrict__ xyz, long i, double (&v)[9], int& bad) const {
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      const double m = res[6 + c] / dn;
+      const float x = xyz[3 * i + c];
+      bad |= !finite_f32(x);
+      v[c] = fmin(v[c], (double)x);
+      v[3 + c] = fmax(v[3 + c], (double)x);
+      v[6 + c] += (double)x;
+    }
+  }
+  __device__ void write(const double (&v)[9], long n) const {
+#pragma unroll
+    for (int c = 0; c < 6; ++c) stats_f32[c] = (float)v[c];        // (exact: the minimum of float32 values)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const double m = v[6 + c] / (double)n;
       stats_f64[c] = m;
       centroid[c] = (float)m;
     }
     stats_f64[3] = NAN; stats_f64[4] = NAN;
-  } else if (PASS == 1) {
-    stats_f64[3] = res[0] / dn;
-  } else {
-    stats_f64[4] = sqrt(res[0] / dn);
   }
-}
+};
+
+// SQUARED false: the sum of d -> stats_f64[3] = mean d.  SQUARED true: the sum of (d - mean d)^2 -> stats_f64[4] = std d.
+template <bool SQUARED>
+struct DistancePass {
+  typedef double T;
+  static constexpr int K = 1;
+  static constexpr int op(int) { return PART_SUM; }
+  double* stats_f64;
+  __device__ void point(const float* __restrict__ xyz, long i, double (&v)[1], int&) const {
+#pragma clang fp contract(off)
+    const double d = centre_distance(xyz, i, stats_f64[0], stats_f64[1]);
+    const double t = d - stats_f64[3];
+    v[0] += SQUARED ? t * t : d;
+  }
+  __device__ void write(const double (&v)[1], long n) const {
+    const double m = v[0] / (double)n;
+    stats_f64[SQUARED ? 4 : 3] = SQUARED ? sqrt(m) : m;
+  }
+};
 
 // ---- rows --------------------------------------------------------------------------------------------------------------
 struct RowArgs {
@@ -291,20 +220,10 @@ struct StatsWs {
   double* partials;          // [blocks, 9]
   int blocks;
   StatsWs(Carve& w, long n) {
-    blocks = std::min(spg_cdiv(std::max<long>(n, 1), PR_BLOCK), PR_MAX_BLOCKS);
+    blocks = part_reduce_blocks(n);
     partials = w.take_n<double>((size_t)blocks * 9);
   }
 };
-
-template <int PASS>
-int stats_pass(const float* xyz, long n, const StatsWs& l, float* stats_f32, double* stats_f64, float* centroid, int32_t* error_flag,
-               hipStream_t st) {
-  hipLaunchKernelGGL(stats_partial_kernel<PASS>, dim3(l.blocks), dim3(PR_BLOCK), 0, st, xyz, n, (const double*)stats_f64, l.partials, error_flag);
-  SPG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(stats_final_kernel<PASS>, dim3(1), dim3(PR_BLOCK), 0, st, (const double*)l.partials, l.blocks, n, stats_f32, stats_f64, centroid);
-  SPG_LAUNCH_CHECK();
-  return 0;
-}
 
 }  // namespace
 
@@ -323,10 +242,10 @@ extern "C" int spg_parsed_stats(const float* xyz, long n, int with_distance, flo
   SPG_CHECK_ARG(w.ok, "workspace too small (spg_parsed_workspace_bytes(n))");
   hipStream_t st = (hipStream_t)stream;
   SPG_RP(hipMemsetAsync(error_flag, 0, sizeof(int32_t), st));
-  if (int rc = stats_pass<0>(xyz, n, l, stats_f32, stats_f64, centroid, error_flag, st)) return rc;
+  if (int rc = part_reduce(StatsPass0{stats_f32, stats_f64, centroid}, xyz, n, l.partials, l.blocks, error_flag, st)) return rc;
   if (with_distance) {
-    if (int rc = stats_pass<1>(xyz, n, l, stats_f32, stats_f64, centroid, error_flag, st)) return rc;
-    if (int rc = stats_pass<2>(xyz, n, l, stats_f32, stats_f64, centroid, error_flag, st)) return rc;
+    if (int rc = part_reduce(DistancePass<false>{stats_f64}, xyz, n, l.partials, l.blocks, nullptr, st)) return rc;
+    if (int rc = part_reduce(DistancePass<true>{stats_f64}, xyz, n, l.partials, l.blocks, nullptr, st)) return rc;
   }
   return 0;
 }
@@ -364,7 +283,7 @@ extern "C" int spg_class_count(const void* labels, int labels_signed, long n, in
   hipStream_t st = (hipStream_t)stream;
   SPG_RP(hipMemsetAsync(count, 0, sizeof(int64_t) * (size_t)n_classes, st));
   if (n == 0) return 0;
-  const dim3 grid(std::min(spg_cdiv(n, PR_BLOCK), PR_MAX_BLOCKS)), blk(PR_BLOCK);
+  const dim3 grid(part_reduce_blocks(n)), blk(PR_BLOCK);
   if (labels_signed) hipLaunchKernelGGL(class_count_kernel<int32_t>, grid, blk, 0, st, (const int32_t*)labels, n, n_classes, (u64*)count);
   else hipLaunchKernelGGL(class_count_kernel<uint32_t>, grid, blk, 0, st, (const uint32_t*)labels, n, n_classes, (u64*)count);
   SPG_LAUNCH_CHECK();

@@ -1,5 +1,6 @@
-// Shared plumbing of the partition-pipeline units (spg_spgraph, spg_knn, spg_edgeloss, spg_parteval, spg_tiles): the workspace
-// convention, the rocPRIM scratch-size queries and the float helpers whose rounding the reference fixes.
+// Shared plumbing of the partition-pipeline units (spg_spgraph, spg_knn, spg_edgeloss, spg_parteval, spg_tiles, spg_structure,
+// spg_plane, spg_parsed): the workspace convention, the rocPRIM scratch-size queries, the float helpers whose rounding the
+// reference fixes, and the fixed-order reduction.
 //
 // Workspace convention: every entry point that takes a workspace describes it ONCE, as a struct whose
 // constructor takes a Carve and the dimensions and performs the take() calls.  spg_*_workspace_bytes runs that constructor on a
@@ -9,6 +10,8 @@
 // The first section (align256, bits_of, Carve) is plain C++ and compiles without HIP; the rest needs hipcc.
 #pragma once
 #include <algorithm>
+#include <cfloat>
+#include <cmath>
 #include <cstddef>
 
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -112,5 +115,127 @@ __device__ __forceinline__ float sumsq3_rn_f32(float dx, float dy, float dz) {
   const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
   const float xy = xx + yy;
   return xy + zz;
+}
+
+__device__ __forceinline__ bool finite_f32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+
+// ---- the fixed-order reduction ----
+// Workgroups of PART_BLOCK threads, at most PART_MAX_BLOCKS of them with a grid stride beyond; inside a workgroup the xor
+// butterfly 32, 16, ..., 1 in every wave, then waves 0, 1, 2, 3 in that order through LDS.  The grid depends on n alone, there is no
+// floating-point atomic and no waiting between workgroups: the same input gives the same bits.
+constexpr int PART_BLOCK = 256;
+constexpr int PART_WAVES = PART_BLOCK / 64;
+constexpr int PART_MAX_BLOCKS = 1024;
+inline int part_reduce_blocks(long n) { return std::min(spg_cdiv(std::max<long>(n, 1), PART_BLOCK), PART_MAX_BLOCKS); }
+
+enum { PART_MIN, PART_MAX, PART_SUM };
+template <int OP> struct PartAll { static constexpr int op(int) { return OP; } };      // every component by the same operation
+
+__device__ __forceinline__ float part_min(float a, float b) { return fminf(a, b); }
+__device__ __forceinline__ double part_min(double a, double b) { return fmin(a, b); }
+__device__ __forceinline__ float part_max(float a, float b) { return fmaxf(a, b); }
+__device__ __forceinline__ double part_max(double a, double b) { return fmax(a, b); }
+// (op is an argument so that a loop over components can pass Ops::op(c); it is a constant at every call and the branch folds away)
+template <typename T>
+__device__ __forceinline__ T part_combine(int op, T a, T b) { return op == PART_MIN ? part_min(a, b) : op == PART_MAX ? part_max(a, b) : a + b; }
+template <typename T>
+__device__ __forceinline__ T part_identity(int op) { return op == PART_MIN ? (T)INFINITY : op == PART_MAX ? (T)-INFINITY : (T)0; }
+
+// the wave's value in every lane (a + b and b + a are one value, so all lanes hold the same bits)
+template <typename T>
+__device__ __forceinline__ T wave_reduce(int op, T v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v = part_combine(op, v, __shfl_xor(v, off, 64));
+  return v;
+}
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) { return wave_reduce(PART_SUM, v); }
+
+// the workgroup's K values in every thread; component c combines by Ops::op(c).  lds: [PART_WAVES][K], free on entry; one barrier.
+template <typename Ops, typename T, int K>
+__device__ __forceinline__ void block_reduce(T (&v)[K], T (*lds)[K]) {
+#pragma unroll
+  for (int c = 0; c < K; ++c) {
+    v[c] = wave_reduce(Ops::op(c), v[c]);
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6][c] = v[c];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < K; ++c) {
+    v[c] = lds[0][c];
+#pragma unroll
+    for (int w = 1; w < PART_WAVES; ++w) v[c] = part_combine(Ops::op(c), v[c], lds[w][c]);
+  }
+}
+
+// block-wide OR of `bad`, then thread 0 sets `bits` in the error word.  Every thread of the workgroup calls it.
+__device__ __forceinline__ void block_report(int bad, int32_t* err, int bits) {
+  bad = __syncthreads_or(bad);
+  if (threadIdx.x == 0 && bad) atomicOr(err, bits);
+}
+
+// The two-phase pass over the points of a scene.  A pass P is a small struct passed by value:
+//   typedef T; static constexpr int K; static constexpr int op(int c);        K values of type T, component c combined by op(c)
+//   __device__ void point(const float* xyz, long i, T (&v)[K], int& bad) const   what point i contributes; bad |= a coordinate is not finite
+//   __device__ void write(const T (&v)[K], long n) const                         thread 0 of the final workgroup: the results
+// part_partial_kernel leaves one row of K partials per workgroup, part_final_kernel is ONE workgroup over the rows in the same shape.
+template <typename P>
+__global__ __launch_bounds__(PART_BLOCK) void part_partial_kernel(P p, const float* __restrict__ xyz, long n,
+                                                                  typename P::T* __restrict__ partials, int32_t* __restrict__ err) {
+  typedef typename P::T T;
+  __shared__ T lds[PART_WAVES][P::K];
+  T v[P::K];
+#pragma unroll
+  for (int c = 0; c < P::K; ++c) v[c] = part_identity<T>(P::op(c));
+  int bad = 0;
+  for (long i = (long)blockIdx.x * PART_BLOCK + threadIdx.x; i < n; i += (long)gridDim.x * PART_BLOCK) p.point(xyz, i, v, bad);
+  if (err != nullptr) block_report(bad, err, 1);
+  block_reduce<P>(v, lds);
+  if (threadIdx.x != 0) return;
+#pragma unroll
+  for (int c = 0; c < P::K; ++c) partials[P::K * (long)blockIdx.x + c] = v[c];
+}
+
+template <typename P>
+__global__ __launch_bounds__(PART_BLOCK) void part_final_kernel(P p, const typename P::T* __restrict__ partials, int nb, long n) {
+  typedef typename P::T T;
+  __shared__ T lds[PART_WAVES][P::K];
+  T v[P::K];
+#pragma unroll
+  for (int c = 0; c < P::K; ++c) v[c] = part_identity<T>(P::op(c));
+  for (int b = threadIdx.x; b < nb; b += PART_BLOCK) {
+#pragma unroll
+    for (int c = 0; c < P::K; ++c) v[c] = part_combine(P::op(c), v[c], partials[P::K * (long)b + c]);
+  }
+  block_reduce<P>(v, lds);
+  if (threadIdx.x == 0) p.write(v, n);
+}
+
+// err: the error word whose bit 0 reports a coordinate that is not finite, or null for a pass that does not check
+template <typename P>
+int part_reduce(const P& p, const float* xyz, long n, typename P::T* partials, int blocks, int32_t* err, hipStream_t st) {
+  hipLaunchKernelGGL(part_partial_kernel<P>, dim3(blocks), dim3(PART_BLOCK), 0, st, p, xyz, n, partials, err);
+  SPG_LAUNCH_CHECK();
+  hipLaunchKernelGGL(part_final_kernel<P>, dim3(1), dim3(PART_BLOCK), 0, st, p, (const typename P::T*)partials, blocks, n);
+  SPG_LAUNCH_CHECK();
+  return 0;
+}
+
+// per-axis minimum / maximum of xyz [n, 3] into mm[0..2] / mm[3..5] as ordered bits (integer atomics: the order does not matter);
+// any grid of whole waves.  -> a coordinate this thread read is not finite
+__device__ __forceinline__ bool axis_minmax(const float* __restrict__ xyz, long n, unsigned* __restrict__ mm) {
+  float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+  bool bad = false;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+    for (int d = 0; d < 3; ++d) {
+      const float v = xyz[3 * i + d];
+      bad |= !finite_f32(v);
+      lo[d] = fminf(lo[d], v); hi[d] = fmaxf(hi[d], v);
+    }
+  for (int d = 0; d < 3; ++d) {
+    lo[d] = wave_reduce(PART_MIN, lo[d]); hi[d] = wave_reduce(PART_MAX, hi[d]);
+    if ((threadIdx.x & 63) == 0) { atomicMin(&mm[d], ordered_bits(lo[d])); atomicMax(&mm[3 + d], ordered_bits(hi[d])); }
+  }
+  return bad;
 }
 #endif  // __HIPCC__

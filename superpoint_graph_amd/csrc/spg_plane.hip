@@ -3,8 +3,8 @@
 // one and takes elevation = z - plane(x, y).  Restated here (tests/plane_restatement.py is the same text in
 // numpy).  Two entry points, with the one host read the sizes need (the number of low points) between them:
 //
-// spg_plane_low   finite check and min z (two phases, as the frame of spg_structure.hip), the flags (z - min z) < low_height in
-//                 float32, and a stable compaction of the indices (rocprim::select keeps the order) -> low_index, n_low.
+// spg_plane_low   finite check and min z (the two-phase pass of spg_part.h), the flags (z - min z) < low_height in float32, and a
+//                 stable compaction of the indices (rocprim::select keeps the order) -> low_index, n_low.
 // spg_plane_fit   threshold  two radix sorts of order-preserving float bits and the middle element(s): median(|y - median(y)|) in
 //                            float32 with numpy's even rule (a + b) / 2 -- bit for bit.
 //                 planes     one lane per trial: the least-squares plane through its three points (centred second moments, 2 x 2;
@@ -13,8 +13,8 @@
 //                 trials     points x trials.  A workgroup reads its PL_BLOCK * PL_PER_LANE low points ONCE into registers and
 //                            runs every trial over them: the plane parameters come from LDS (one broadcast read per trial), the
 //                            inlier count goes through ballot / popcount, the three float64 sums of R^2 (r^2, q, q^2 with q = y -
-//                            median: shifted, so that the total sum of squares does not cancel) through a wave butterfly and the
-//                            four waves in order into partials [blocks][T].
+//                            median: shifted, so that the total sum of squares does not cancel) through wave_sum and the four
+//                            waves in order (the order of spg_part.h) into partials [blocks][T].
 //                 replay     ONE wave: adds the partials block by block (a fixed order), forms R^2 as r2_score does and replays
 //                            sklearn's acceptance loop (count < best: skip; equal count and lower score: skip; else accept and
 //                            shrink max_trials by _dynamic_max_trials).  No host loop.
@@ -33,55 +33,29 @@
 
 namespace {
 
-constexpr int PL_BLOCK = 256;
-constexpr int PL_WAVES = PL_BLOCK / 64;
+constexpr int PL_BLOCK = PART_BLOCK;
+constexpr int PL_WAVES = PART_WAVES;
 constexpr int PL_PER_LANE = 4;
 constexpr int PL_POINTS = PL_BLOCK * PL_PER_LANE;     // low points per workgroup of the trial and final passes
 constexpr int PL_TILE = 128;                          // trials whose planes and wave sums are in LDS at once
 constexpr int PL_MAX_TRIALS = 1024;
-constexpr int PL_MAX_BLOCKS = 1024;                   // workgroups of the min-z pass (grid-stride beyond)
 constexpr double PL_EPS32 = 1.1920928955078125e-07;   // np.finfo(np.float32).eps
 constexpr double PL_EPS64 = 2.220446049250313e-16;    // sklearn's _EPSILON = np.spacing(1)
 
-__device__ __forceinline__ bool finite_f32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
 // ---- low points --------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float block_min(float v, float* lds) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = fminf(v, __shfl_xor(v, off, 64));
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float r = lds[0];
-#pragma unroll
-  for (int w = 1; w < PL_WAVES; ++w) r = fminf(r, lds[w]);
-  return r;
-}
-
-__global__ __launch_bounds__(PL_BLOCK) void zmin_partial_kernel(const float* __restrict__ xyz, long n, float* __restrict__ partials,
-                                                                int32_t* __restrict__ err) {
-  __shared__ float lds[PL_WAVES];
-  float v = INFINITY;
-  int bad = 0;
-  for (long i = (long)blockIdx.x * PL_BLOCK + threadIdx.x; i < n; i += (long)gridDim.x * PL_BLOCK) {
+// the pass (spg_part.h) of min z and the finite check
+struct ZMinPass {
+  typedef float T;
+  static constexpr int K = 1;
+  static constexpr int op(int) { return PART_MIN; }
+  float* zmin;
+  __device__ void point(const float* __restrict__ xyz, long i, float (&v)[1], int& bad) const {
     const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
     bad |= !(finite_f32(x) && finite_f32(y) && finite_f32(z));
-    v = fminf(v, z);
+    v[0] = fminf(v[0], z);
   }
-  bad = __syncthreads_or(bad);
-  v = block_min(v, lds);
-  if (threadIdx.x == 0) {
-    partials[blockIdx.x] = v;
-    if (bad) atomicOr(err, 1);
-  }
-}
-
-__global__ __launch_bounds__(PL_BLOCK) void zmin_final_kernel(const float* __restrict__ partials, int nb, float* __restrict__ zmin) {
-  __shared__ float lds[PL_WAVES];
-  float v = INFINITY;
-  for (int b = threadIdx.x; b < nb; b += PL_BLOCK) v = fminf(v, partials[b]);
-  v = block_min(v, lds);
-  if (threadIdx.x == 0) zmin[0] = v;
-}
+  __device__ void write(const float (&v)[1], long) const { zmin[0] = v[0]; }
+};
 
 __global__ __launch_bounds__(PL_BLOCK) void low_flags_kernel(const float* __restrict__ xyz, long n, const float* __restrict__ zmin,
                                                              float low_height, int32_t* __restrict__ iota, uint8_t* __restrict__ flags) {
@@ -184,12 +158,6 @@ __global__ __launch_bounds__(64) void planes_kernel(const float* __restrict__ xy
 }
 
 // ---- trials ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // the workgroup's PL_POINTS low points into registers (lane-consecutive indices); ok: the point exists
 __device__ __forceinline__ void load_points(const float* __restrict__ xyz, const int32_t* __restrict__ low_index, long n_low,
                                             double (&x)[PL_PER_LANE], double (&y)[PL_PER_LANE], double (&z)[PL_PER_LANE],
@@ -418,7 +386,7 @@ struct LowWs {
   size_t tmp_bytes;
   int blocks;
   LowWs(Carve& w, long n) {
-    blocks = std::min(spg_cdiv(std::max<long>(n, 1), PL_BLOCK), PL_MAX_BLOCKS);
+    blocks = part_reduce_blocks(n);
     zpart = w.take_n<float>((size_t)blocks);
     zmin = w.take_n<float>(1);
     iota = w.take_n<int32_t>((size_t)n);
@@ -471,10 +439,7 @@ extern "C" int spg_plane_low(const float* xyz, long n, float low_height, int32_t
   SPG_CHECK_ARG(w.ok, "workspace too small (spg_plane_workspace_bytes(n, -1, 0))");
   hipStream_t st = (hipStream_t)stream;
   SPG_RP(hipMemsetAsync(error_flag, 0, sizeof(int32_t), st));
-  hipLaunchKernelGGL(zmin_partial_kernel, dim3(l.blocks), dim3(PL_BLOCK), 0, st, xyz, n, l.zpart, error_flag);
-  SPG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(zmin_final_kernel, dim3(1), dim3(PL_BLOCK), 0, st, (const float*)l.zpart, l.blocks, l.zmin);
-  SPG_LAUNCH_CHECK();
+  if (int rc = part_reduce(ZMinPass{l.zmin}, xyz, n, l.zpart, l.blocks, error_flag, st)) return rc;
   hipLaunchKernelGGL(low_flags_kernel, dim3(spg_cdiv(n, PL_BLOCK)), dim3(PL_BLOCK), 0, st, xyz, n, (const float*)l.zmin, low_height, l.iota,
                      l.flags);
   SPG_LAUNCH_CHECK();

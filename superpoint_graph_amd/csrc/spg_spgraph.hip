@@ -118,12 +118,6 @@ __global__ void comp_offsets_kernel(const u64* __restrict__ keys, long n, int n_
   off[c] = lo;
 }
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);      // xor butterfly: every lane gets the same fixed-order sum
-  return v;
-}
-
 __device__ __forceinline__ bool same_point(const float* __restrict__ xyz, unsigned a, unsigned b) {
   return xyz[3 * (long)a] == xyz[3 * (long)b] && xyz[3 * (long)a + 1] == xyz[3 * (long)b + 1] &&
          xyz[3 * (long)a + 2] == xyz[3 * (long)b + 2];
@@ -173,7 +167,7 @@ __global__ __launch_bounds__(256) void superpoints_kernel(const float* __restric
       m += 1.0; sx += (double)xyz[3 * (long)p]; sy += (double)xyz[3 * (long)p + 1]; sz += (double)xyz[3 * (long)p + 2];
     }
   }
-  m = wave_sum_d(m); sx = wave_sum_d(sx); sy = wave_sum_d(sy); sz = wave_sum_d(sz);
+  m = wave_sum(m); sx = wave_sum(sx); sy = wave_sum(sy); sz = wave_sum(sz);
   if (lane == 0) point_count[c] = (u64)(e - b);      // graphs.py:149 (duplicates included)
   if (m < 0.5) {                                      // empty component: the reference's loop would fail; zeros
     if (lane == 0) {
@@ -220,7 +214,7 @@ __global__ __launch_bounds__(256) void superpoints_kernel(const float* __restric
       cxx += dx * dx; cxy += dx * dy; cxz += dx * dz; cyy += dy * dy; cyz += dy * dz; czz += dz * dz;
     }
   }
-  cxx = wave_sum_d(cxx); cxy = wave_sum_d(cxy); cxz = wave_sum_d(cxz); cyy = wave_sum_d(cyy); cyz = wave_sum_d(cyz); czz = wave_sum_d(czz);
+  cxx = wave_sum(cxx); cxy = wave_sum(cxy); cxz = wave_sum(cxz); cyy = wave_sum(cyy); cyz = wave_sum(cyz); czz = wave_sum(czz);
   if (lane == 0) {
     const double f = 1.0 / (m - 1.0);
     double ev[3];
@@ -280,8 +274,8 @@ __global__ __launch_bounds__(256) void superedges_kernel(const u64* __restrict__
   }
   const double cnt = (double)(e - b);
   double mean[3];
-  for (int d = 0; d < 3; ++d) mean[d] = wave_sum_d(sd[d]) / cnt;
-  sn = wave_sum_d(sn);
+  for (int d = 0; d < 3; ++d) mean[d] = wave_sum(sd[d]) / cnt;
+  sn = wave_sum(sn);
   double var[3] = {0.0, 0.0, 0.0};
   if (e - b > 1) {
     for (long j = b + lane; j < e; j += 64) {
@@ -292,7 +286,7 @@ __global__ __launch_bounds__(256) void superedges_kernel(const u64* __restrict__
         var[d] += dv * dv;
       }
     }
-    for (int d = 0; d < 3; ++d) var[d] = wave_sum_d(var[d]) / cnt;      // np.std: ddof = 0
+    for (int d = 0; d < 3; ++d) var[d] = wave_sum(var[d]) / cnt;      // np.std: ddof = 0
   }
   if (lane != 0) return;
   o.source[s] = (uint32_t)cs;
@@ -432,15 +426,8 @@ struct SuperpointsWs {      // which = 2: two key arrays, two index arrays, comp
 // it; a stable radix sort by (bin_x, bin_y, bin_z) keeps the points of a voxel in input order, so ONE thread per voxel adds its
 // positions in the reference's order with float32 additions (no reassociation, no fma) -- the same rounding as the serial loop.
 // -------------------------------------------------------------------------------------------------------------------
-__global__ void minmax_kernel(const float* __restrict__ xyz, long n, unsigned* __restrict__ mm) {      // mm[0..2] = min, mm[3..5] = max (ordered bits)
-  float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
-    for (int d = 0; d < 3; ++d) { const float v = xyz[3 * i + d]; lo[d] = fminf(lo[d], v); hi[d] = fmaxf(hi[d], v); }
-  for (int d = 0; d < 3; ++d) {
-    for (int o = 32; o >= 1; o >>= 1) { lo[d] = fminf(lo[d], __shfl_xor(lo[d], o, 64)); hi[d] = fmaxf(hi[d], __shfl_xor(hi[d], o, 64)); }
-    if ((threadIdx.x & 63) == 0) { atomicMin(&mm[d], ordered_bits(lo[d])); atomicMax(&mm[3 + d], ordered_bits(hi[d])); }
-  }
-}
+// mm[0..2] = min, mm[3..5] = max (ordered bits)
+__global__ void minmax_kernel(const float* __restrict__ xyz, long n, unsigned* __restrict__ mm) { (void)axis_minmax(xyz, n, mm); }
 
 __global__ void voxel_keys_kernel(const float* __restrict__ xyz, long n, const unsigned* __restrict__ mm, float voxel, u64* __restrict__ keys,
                                   unsigned* __restrict__ idx, unsigned* __restrict__ flag) {

@@ -3,10 +3,9 @@
 // connected components, compute_geof).  Three entry points, all streaming and memory-bound: every global access is coalesced
 // (consecutive lanes, consecutive addresses) and nothing is read twice.
 //
-// Frame (spg_structure_frame): min z, min x, min y, max x, max y of xyz [n, 3] in two phases -- frame_partial_kernel: a grid-stride
-//   pass, wave shuffles, four waves through LDS, one row of five floats per workgroup; frame_final_kernel: one workgroup over those
-//   rows.  Min and max do not depend on the order, so the values are those of np.min / np.max (up to the sign of a zero, which
-//   numpy leaves open too).  A coordinate that is not finite sets bit 0 of the error word.
+// Frame (spg_structure_frame): min z, min x, min y, max x, max y of xyz [n, 3] by the two-phase pass of spg_part.h (FramePass).  Min
+//   and max do not depend on the order, so the values are those of np.min / np.max (up to the sign of a zero, which numpy leaves
+//   open too).  A coordinate that is not finite sets bit 0 of the error word.
 // Vertices (spg_structure_vertices): vertices_kernel, 256 vertices per workgroup.
 //   values   one lane per vertex: elevation = z - min z; xyn = (xy - mi) / ((ma - mi) + 1e-8f), every step rounded to float32
 //            on its own and ONE correctly rounded division (numpy keeps float32 when a float32 array meets a Python scalar);
@@ -28,67 +27,26 @@
 
 namespace {
 
-constexpr int ST_BLOCK = 256;
-constexpr int ST_MAX_BLOCKS = 1024;       // workgroups of the frame's first phase (grid-stride beyond)
-
-__device__ __forceinline__ bool finite_f32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+constexpr int ST_BLOCK = PART_BLOCK;
 
 // ---- frame -------------------------------------------------------------------------------------------------------------
-// v[0..2]: minima (z, x, y), v[3..4]: maxima (x, y) -> the workgroup's values in every lane of wave 0
-__device__ __forceinline__ void frame_block_reduce(float (&v)[5], float (*lds)[5]) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-#pragma unroll
-    for (int c = 0; c < 5; ++c) {
-      const float o = __shfl_xor(v[c], off, 64);
-      v[c] = c < 3 ? fminf(v[c], o) : fmaxf(v[c], o);
-    }
-  }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) {
-#pragma unroll
-    for (int c = 0; c < 5; ++c) lds[wave][c] = v[c];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int c = 0; c < 5; ++c) {
-    float r = lds[0][c];
-#pragma unroll
-    for (int w = 1; w < ST_BLOCK / 64; ++w) r = c < 3 ? fminf(r, lds[w][c]) : fmaxf(r, lds[w][c]);
-    v[c] = r;
-  }
-}
-
-__global__ __launch_bounds__(ST_BLOCK) void frame_partial_kernel(const float* __restrict__ xyz, long n, float* __restrict__ partials,
-                                                                 int32_t* __restrict__ err) {
-  __shared__ float lds[ST_BLOCK / 64][5];
-  float v[5] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY};
-  int bad = 0;
-  for (long i = (long)blockIdx.x * ST_BLOCK + threadIdx.x; i < n; i += (long)gridDim.x * ST_BLOCK) {
+// the pass (spg_part.h) of the minima (z, x, y), the maxima (x, y) and the finite check -> frame [5]
+struct FramePass {
+  typedef float T;
+  static constexpr int K = 5;
+  static constexpr int op(int c) { return c < 3 ? PART_MIN : PART_MAX; }
+  float* frame;
+  __device__ void point(const float* __restrict__ xyz, long i, float (&v)[5], int& bad) const {
     const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
     bad |= !(finite_f32(x) && finite_f32(y) && finite_f32(z));
     v[0] = fminf(v[0], z); v[1] = fminf(v[1], x); v[2] = fminf(v[2], y);
     v[3] = fmaxf(v[3], x); v[4] = fmaxf(v[4], y);
   }
-  bad = __syncthreads_or(bad);
-  frame_block_reduce(v, lds);
-  if (threadIdx.x < 5) partials[5 * (long)blockIdx.x + threadIdx.x] = v[threadIdx.x];
-  if (threadIdx.x == 0 && bad) atomicOr(err, 1);
-}
-
-__global__ __launch_bounds__(ST_BLOCK) void frame_final_kernel(const float* __restrict__ partials, int nb, float* __restrict__ frame) {
-  __shared__ float lds[ST_BLOCK / 64][5];
-  float v[5] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY};
-  for (int b = threadIdx.x; b < nb; b += ST_BLOCK) {
+  __device__ void write(const float (&v)[5], long) const {
 #pragma unroll
-    for (int c = 0; c < 5; ++c) {
-      const float o = partials[5 * (long)b + c];
-      v[c] = c < 3 ? fminf(v[c], o) : fmaxf(v[c], o);
-    }
+    for (int c = 0; c < 5; ++c) frame[c] = v[c];
   }
-  frame_block_reduce(v, lds);
-  if (threadIdx.x < 5) frame[threadIdx.x] = v[threadIdx.x];
-}
+};
 
 // ---- vertices ----------------------------------------------------------------------------------------------------------
 struct VertexArgs {
@@ -178,15 +136,14 @@ __global__ __launch_bounds__(ST_BLOCK) void edges_kernel(const int32_t* __restri
       }
     }
   }
-  bad = __syncthreads_or(bad);
-  if (threadIdx.x == 0 && bad) atomicOr(err, 2);
+  block_report(bad, err, 2);
 }
 
 struct FrameWs {
   float* partials;           // [blocks, 5]
   int blocks;
   FrameWs(Carve& w, long n) {
-    blocks = std::min(spg_cdiv(std::max<long>(n, 1), ST_BLOCK), ST_MAX_BLOCKS);
+    blocks = part_reduce_blocks(n);
     partials = w.take_n<float>((size_t)blocks * 5);
   }
 };
@@ -208,10 +165,7 @@ extern "C" int spg_structure_frame(const float* xyz, long n, float* frame, int32
   SPG_CHECK_ARG(w.ok, "workspace too small (spg_structure_frame_workspace_bytes)");
   hipStream_t st = (hipStream_t)stream;
   SPG_RP(hipMemsetAsync(error_flag, 0, sizeof(int32_t), st));
-  hipLaunchKernelGGL(frame_partial_kernel, dim3(l.blocks), dim3(ST_BLOCK), 0, st, xyz, n, l.partials, error_flag);
-  SPG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(frame_final_kernel, dim3(1), dim3(ST_BLOCK), 0, st, (const float*)l.partials, l.blocks, frame);
-  SPG_LAUNCH_CHECK();
+  if (int rc = part_reduce(FramePass{frame}, xyz, n, l.partials, l.blocks, error_flag, st)) return rc;
   return 0;
 }
 

@@ -23,9 +23,15 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return t.data_ptr()
 
 
-def _req(t: torch.Tensor, dtype=None, name='tensor'):
-    if not t.is_cuda:
+def _on_gpu(t, name):
+    """The device test of _req on its own, for an argument that is converted before _req sees it."""
+    if not torch.is_tensor(t) or not t.is_cuda:
         raise RuntimeError(f'{name} must live on the GPU: the superpoint_graph_amd kernels have no CPU path')
+    return t
+
+
+def _req(t: torch.Tensor, dtype=None, name='tensor'):
+    _on_gpu(t, name)
     if t.device.index != torch.cuda.current_device():
         # the kernels are launched on the CURRENT device's stream; a tensor of another GPU would be an invalid access
         raise RuntimeError(f'{name} lives on cuda:{t.device.index} but the current device is cuda:{torch.cuda.current_device()}; '
@@ -1182,8 +1188,7 @@ def edge_loss(diff, is_transition, weights, loss='TVH_zhang', dist_type='euclidi
     float32 scalars; differentiable wrt diff."""
     intra, inter = _loss_codes(loss)
     code = _dist_code(dist_type)
-    if not diff.is_cuda:
-        raise RuntimeError('diff must live on the GPU: the superpoint_graph_amd kernels have no CPU path')
+    _on_gpu(diff, 'diff')
     if diff.dim() != 1:
         raise ValueError(f'diff must be [E], got {tuple(diff.shape)}')
     E = int(diff.numel())
@@ -1197,8 +1202,7 @@ def contrastive_edge_loss(embeddings, graph: EdgeGraph, is_transition, weights, 
     intra, inter = _loss_codes(loss)
     code = _dist_code(dist_type)
     graph._use()
-    if not embeddings.is_cuda:
-        raise RuntimeError('embeddings must live on the GPU: the superpoint_graph_amd kernels have no CPU path')
+    _on_gpu(embeddings, 'embeddings')
     return _ContrastiveEdgeLossFunction.apply(embeddings, graph, _edge_vec(is_transition, torch.uint8, graph.E, 'is_transition'),
                                               _edge_vec(weights, torch.float32, graph.E, 'weights'), intra, inter, code)
 
@@ -1226,8 +1230,7 @@ def crosspartition_weights(graph: EdgeGraph, pred_in_component, is_transition, f
     return_components: also (in_component_x i32 [n], n_components int, component_size i32)."""
     graph._use()
     is_transition = _edge_vec(is_transition, torch.uint8, graph.E, 'is_transition')
-    if not pred_in_component.is_cuda:
-        raise RuntimeError('pred_in_component must live on the GPU: the superpoint_graph_amd kernels have no CPU path')
+    _on_gpu(pred_in_component, 'pred_in_component')
     pred = _req(pred_in_component.to(torch.int32).contiguous(), torch.int32, 'pred_in_component')
     L, dev, n = lib(), graph.device, graph.n
     if pred.shape != (n,):
@@ -1255,8 +1258,7 @@ _RELAX_MODES = {'reference': 0, 'symmetric': 1}
 
 def _vertex_vec(t, n, name):
     """An integer [n] device tensor as contiguous int32 (the values must fit: ids and labels below 2^31)."""
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise RuntimeError(f'{name} must live on the GPU: the superpoint_graph_amd kernels have no CPU path')
+    _on_gpu(t, name)
     if t.dtype.is_floating_point or t.dtype == torch.bool:
         raise TypeError(f'{name} must be an integer tensor, got {t.dtype}')
     if t.shape != (n,):
@@ -1266,8 +1268,7 @@ def _vertex_vec(t, n, name):
 
 def _indicator(t, E, name):
     """A bool / uint8 [E] device tensor as contiguous uint8 (bool is reinterpreted, not copied)."""
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise RuntimeError(f'{name} must live on the GPU: the superpoint_graph_amd kernels have no CPU path')
+    _on_gpu(t, name)
     if t.dtype not in (torch.bool, torch.uint8):
         raise TypeError(f'{name} must be bool or uint8, got {t.dtype}')
     if t.shape != (E,):
@@ -1312,8 +1313,7 @@ class PartitionIndex:
 
 
 def _label_majority(index, labels):
-    if not torch.is_tensor(labels) or not labels.is_cuda:
-        raise RuntimeError('labels must live on the GPU: the superpoint_graph_amd kernels have no CPU path')
+    _on_gpu(labels, 'labels')
     if labels.dim() != 2 or labels.shape[0] != index.n or labels.shape[1] < 2:
         raise ValueError(f'labels must be [{index.n}, C + 1] (column 0 = unlabelled), got {tuple(labels.shape)}')
     C = int(labels.shape[1]) - 1
@@ -1471,8 +1471,7 @@ _GLOBAL_FEAT_KEYS = ('e', 'rgb', 'XY', 'xy')
 
 
 def _scene_array(t, shape, name):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise RuntimeError(f'{name} must live on the GPU: the superpoint_graph_amd kernels have no CPU path')
+    _on_gpu(t, name)
     if tuple(t.shape) != tuple(shape):
         raise ValueError(f'{name} must be {list(shape)}, got {list(t.shape)}')
     return _req(t.contiguous(), torch.float32, name)
@@ -1491,8 +1490,7 @@ def neighbourhood_tiles(xyz, nei, k: int, rows=None, rgb=None, global_feat='', e
         raise ValueError('xyz must be a [N, 3] tensor')
     N, k = int(xyz.shape[0]), int(k)
     xyz = _scene_array(xyz, (N, 3), 'xyz')
-    if not torch.is_tensor(nei) or not nei.is_cuda:
-        raise RuntimeError('nei must live on the GPU: the superpoint_graph_amd kernels have no CPU path')
+    _on_gpu(nei, 'nei')
     if nei.dtype not in (torch.int32, torch.int64):
         raise TypeError(f'nei must be int32 or int64, got {nei.dtype}')
     if nei.dim() != 2 or nei.shape[0] != N:
@@ -1651,6 +1649,20 @@ def induced_subgraph(graph: EdgeGraph, selected_ver, selected_edg):
 _ID_MODES = {'objects': 1, 'labels': 2, 'given': 3}
 
 
+def _scene_xyz(xyz, who):
+    """xyz as every scene op takes it: float32 [n, 3] on the device, n >= 1 -> n"""
+    _req(xyz, torch.float32, 'xyz')
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] < 1:
+        raise ValueError(f'{who}: xyz must be [n, 3] with n >= 1, got {tuple(xyz.shape)}')
+    return int(xyz.shape[0])
+
+
+def _raise_nonfinite(word):
+    """bit 0 of an error word of the scene ops: sklearn's message for a coordinate that is NaN or infinite"""
+    if word & 1:
+        raise ValueError('Input contains NaN or infinity.')
+
+
 def scene_structure(xyz, knn_idx, k_adj: int, ids=None, hist=None, id_mode='objects', geof=None, rgb=None):
     """What graph_processing.py:main() computes per file between prune, the kNN search and compute_geof (:126, :144-190), on
     device tensors: xyz f32 [n, 3]; knn_idx i32 [n, k_local] as ops.knn returns it (the point itself dropped); the first k_adj
@@ -1664,10 +1676,8 @@ def scene_structure(xyz, knn_idx, k_adj: int, ids=None, hist=None, id_mode='obje
     u8, hard_ids i64 [n], objects i64 [n], elevation f32 [n] (z - min z), xyn f32 [n, 2], geof, rgb (None when not given), and
     graph, the EdgeGraph of the adjacency.  Host reads: the error word after the frame pass (ValueError on NaN / infinity before
     anything else is launched) and after the edges, the EdgeGraph's, and the component count with id_mode 'labels'."""
-    _req(xyz, torch.float32, 'xyz'); _req(knn_idx, torch.int32, 'knn_idx')
-    if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] < 1:
-        raise ValueError(f'scene_structure: xyz must be [n, 3] with n >= 1, got {tuple(xyz.shape)}')
-    n, k_adj = int(xyz.shape[0]), int(k_adj)
+    n, k_adj = _scene_xyz(xyz, 'scene_structure'), int(k_adj)
+    _req(knn_idx, torch.int32, 'knn_idx')
     if knn_idx.dim() != 2 or knn_idx.shape[0] != n:
         raise ValueError(f'scene_structure: knn_idx must be [{n}, k_local], got {tuple(knn_idx.shape)}')
     k_local = int(knn_idx.shape[1])
@@ -1706,8 +1716,7 @@ def scene_structure(xyz, knn_idx, k_adj: int, ids=None, hist=None, id_mode='obje
     err = torch.empty(1, dtype=torch.int32, device=dev)
     ws = _u8_workspace(L.spg_structure_frame_workspace_bytes(n), dev)
     check(L.spg_structure_frame(_ptr(xyz), n, _ptr(frame), _ptr(err), _ptr(ws), ws.numel(), st), 'spg_structure_frame')
-    if int(err.item()) & 1:
-        raise ValueError('Input contains NaN or infinity.')
+    _raise_nonfinite(int(err.item()))
     E = n * k_adj
     out = {'elevation': torch.empty(n, dtype=f32, device=dev), 'xyn': torch.empty(n, 2, dtype=f32, device=dev),
            'hard_ids': torch.empty(n, dtype=i64, device=dev), 'geof': geof, 'nei': knn_idx,
@@ -1771,18 +1780,14 @@ def plane_elevation(xyz, subsets=None, seed: int = 0, max_trials: int = 100, low
     ransac_subsets(n_low, max_trials, seed) on the host.  Every trial is evaluated; sklearn's acceptance loop is replayed on the
     device.  Host reads: n_low with the error word (ValueError on NaN / infinity before anything else), and the error word with
     n_trials / best_trial at the end (ValueError when no trial found a consensus set, IndexError for a subset index)."""
-    _req(xyz, torch.float32, 'xyz')
-    if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] < 1:
-        raise ValueError(f'plane_elevation: xyz must be [n, 3] with n >= 1, got {tuple(xyz.shape)}')
+    n = _scene_xyz(xyz, 'plane_elevation')
     L, dev, st = lib(), xyz.device, _stream()
-    n = int(xyz.shape[0])
     low_index = torch.empty(n, dtype=torch.int32, device=dev)
     head = torch.empty(2, dtype=torch.int32, device=dev)                   # n_low, error word: one read
     ws = _u8_workspace(L.spg_plane_workspace_bytes(n, -1, 0), dev)
     check(L.spg_plane_low(_ptr(xyz), n, float(low_height), _ptr(low_index), _ptr(head), _ptr(head[1:]), _ptr(ws), ws.numel(), st), 'spg_plane_low')
     n_low, err = (int(v) for v in head.tolist())
-    if err & 1:
-        raise ValueError('Input contains NaN or infinity.')
+    _raise_nonfinite(err)
     if n_low < 3:
         raise ValueError(f'`min_samples` may not be larger than number of samples: n_samples = {n_low}.')
     if subsets is None:
@@ -1824,17 +1829,14 @@ def scene_stats(xyz, with_distance: bool = False):
     xyz f32 [n, 3] on the device -> (stats_f32 [6] = min x, y, z, max x, y, z; stats_f64 [5] = mean x, y, z and, with_distance,
     the mean and population standard deviation of the distance to the room centre in float64; centroid f32 [3]), device tensors.
     One host read: the error word (ValueError on NaN / infinity)."""
-    _req(xyz, torch.float32, 'xyz')
-    if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] < 1:
-        raise ValueError(f'scene_stats: xyz must be [n, 3] with n >= 1, got {tuple(xyz.shape)}')
-    L, dev, n = lib(), xyz.device, int(xyz.shape[0])
+    n = _scene_xyz(xyz, 'scene_stats')
+    L, dev = lib(), xyz.device
     s32, s64 = torch.empty(6, dtype=torch.float32, device=dev), torch.empty(5, dtype=torch.float64, device=dev)
     centroid, err = torch.empty(3, dtype=torch.float32, device=dev), torch.empty(1, dtype=torch.int32, device=dev)
     ws = _u8_workspace(L.spg_parsed_workspace_bytes(n), dev)
     check(L.spg_parsed_stats(_ptr(xyz), n, int(bool(with_distance)), _ptr(s32), _ptr(s64), _ptr(centroid), _ptr(err), _ptr(ws), ws.numel(),
                              _stream()), 'spg_parsed_stats')
-    if int(err.item()) & 1:
-        raise ValueError('Input contains NaN or infinity.')
+    _raise_nonfinite(int(err.item()))
     return s32, s64, centroid
 
 
@@ -1852,10 +1854,7 @@ def parsed_points(recipe, xyz, rgb, comp_off, comp_idx, geof=None, elevation=Non
     if recipe not in PARSED_RECIPES:
         raise ValueError(f'parsed_points: recipe must be one of {sorted(PARSED_RECIPES)}, got {recipe!r}')
     code, ncols = PARSED_RECIPES[recipe]
-    _req(xyz, torch.float32, 'xyz')
-    if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] < 1:
-        raise ValueError(f'parsed_points: xyz must be [n, 3] with n >= 1, got {tuple(xyz.shape)}')
-    n, dev = int(xyz.shape[0]), xyz.device
+    n, dev = _scene_xyz(xyz, 'parsed_points'), xyz.device
     _req(rgb, None, 'rgb')
     if rgb.dtype not in (torch.uint8, torch.float32) or rgb.shape != (n, 3):
         raise ValueError(f'parsed_points: rgb must be uint8 or float32 [{n}, 3]')

@@ -25,7 +25,7 @@ import numpy as np
 F32 = np.float32
 N_CLASSES = {'s3dis': 13, 'sema3d': 8, 'vkitti': 13, 'custom': 8}
 REDUCE_BLOCK = 256            # csrc/spg_parsed.hip: PR_BLOCK (threads of a reduction workgroup, rows of a gather workgroup)
-REDUCE_MAX_BLOCKS = 1024      # PR_MAX_BLOCKS: beyond, a workgroup strides over the scene
+REDUCE_MAX_BLOCKS = 1024      # csrc/spg_part.h: PART_MAX_BLOCKS: beyond, a workgroup strides over the scene
 
 
 def room(n, offset=0.0, seed=0):

@@ -1,7 +1,9 @@
-"""Every workspace-taking entry point of the partition units (spg_spgraph, spg_knn, spg_edgeloss, spg_parteval, spg_tiles)
+"""Every workspace-taking entry point of the partition units (spg_spgraph, spg_knn, spg_edgeloss, spg_parteval, spg_tiles,
+spg_plane; spg_structure_frame and spg_parsed_stats by the same helper in tests/test_gpu_structure.py and tests/test_gpu_parsed.py)
 through ctypes: a buffer of exactly spg_*_workspace_bytes bytes is enough and gives, bit for bit, what the ops wrapper
 gives; with one byte less the call is refused before anything is written and the error names the size query.
-Two sizes each: the smallest legal one, and one past a 256-thread block (n = 1 / 257, E = 1 / 300)."""
+Two sizes each: the smallest legal one, and one past a 256-thread block (n = 1 / 257, E = 1 / 300); the plane fit's smallest is
+n = n_low = 3, and its larger one, 1300 low points, is past one workgroup of its trial pass (1024 points), with 1 and 100 trials."""
 import pytest
 import torch
 
@@ -237,3 +239,26 @@ def test_sp_graph_stages(L, n):
                     lambda o, ws, b: L.spg_spg_group_edges(P(cc_keys), P(edge_keys), n_edg, P(o[0]), P(o[1]), P(o[2]), P(o[3]), P(o[4]), ws, b,
                                                            stream()),
                     [(4, one(n_sedg), None)] + ([(1, ref['edges'], n_edg), (3, ref['seg_off'], n_sedg + 1)] if T else []))
+
+
+@pytest.mark.parametrize('n,T', [(3, 1), (1300, 1), (1300, 100)])
+def test_plane_units(L, n, T):
+    from superpoint_graph_amd import ops
+    g = torch.Generator().manual_seed(6)
+    xyz = (torch.rand(n, 3, generator=g) * torch.tensor([10.0, 8.0, 0.3])).cuda()      # z < 0.3: every point is a low point
+    subsets = torch.from_numpy(ops.ransac_subsets(n, T, 0)).to(i32).cuda()
+    ref = ops.plane_elevation(xyz, subsets=subsets)
+    n_low = ref['n_low']
+    assert n_low == n
+    word = lambda *v: torch.tensor(v, dtype=i32, device='cuda')
+    exact_and_short(L, 'spg_plane_workspace_bytes(n, -1, 0)', L.spg_plane_workspace_bytes(n, -1, 0), lambda: fresh((n, i32), (1, i32), (1, i32)),
+                    lambda o, ws, b: L.spg_plane_low(P(xyz), n, 0.5, P(o[0]), P(o[1]), P(o[2]), ws, b, stream()),
+                    [(0, ref['low_index'], n_low), (1, word(n_low), None), (2, word(0), None)])
+    low = ref['low_index'].contiguous()
+    # (the fit ORs into its error word and does not clear it: the caller hands it over as zero)
+    exact_and_short(L, 'spg_plane_workspace_bytes(n, n_low, trials)', L.spg_plane_workspace_bytes(n, n_low, T),
+                    lambda: fresh((n, f32), (2, f64), (1, f64), (1, f32), (n_low, u8), (2, i32)) + [torch.zeros(1, dtype=i32, device='cuda')],
+                    lambda o, ws, b: L.spg_plane_fit(P(xyz), n, P(low), n_low, P(subsets), T, P(o[0]), P(o[1]), P(o[2]), P(o[3]), P(o[4]), P(o[5]),
+                                                     P(o[6]), ws, b, stream()),
+                    [(0, ref['elevation'], None), (1, ref['coef'], None), (2, ref['intercept'], None), (3, ref['threshold'], None),
+                     (4, ref['inlier_mask'], None), (5, word(ref['n_trials'], ref['best_trial']), None), (6, word(0), None)])
