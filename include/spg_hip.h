@@ -814,6 +814,23 @@ int spg_parsed_rows(int recipe, const float* xyz, long n, const void* rgb, int r
  * labels_signed) [n, n_classes + 1]: the first maximum; an all-zero row counts for class 0.  1 <= n_classes <= 4096. */
 int spg_class_count(const void* labels, int labels_signed, long n, int n_classes, int64_t* count, void* stream);
 
+/* ---- neighbourhood sub-sampling of a resident superpoint graph (csrc/spg_sample.hip; reference learning/spg.py:115-144:
+ * permute_vertices -> random_neighborhoods -> k_big_enough, restated in original vertex ids: DESIGN.md section 4.6b).  ends: int32
+ * [E, 2] of spg_edgegraph_build (the edges in file order); 1 <= n < 2^31 - 1, 0 <= E < 2^30.  All pointers are device pointers.
+ * perm int64 [n] (vertex k becomes position perm[k]) or null = the identity; centres int64 [n_centres], ids in the PERMUTED
+ * numbering, or null = every vertex is a member; otherwise the members are the vertices within `order` steps, direction ignored,
+ * of a centre.  Walking the permuted positions, a member is kept while the inclusive count of members with sizes[v] >= minpts
+ * (sizes int64 [n]) is <= hardcutoff; hardcutoff <= 0 = every member is kept (sizes may be null).
+ * -> vids int64 [n] (the first m: the kept vertices in position order; their rank is their new id), edges_out int64 [E, 2], kept
+ * int64 [E] and feats_out f32 [E, F] (the first E' rows: the edges with both ends kept, in file order: relabelled ends, edge id, the
+ * row of feats f32 [E, F], copied; feats / feats_out both null = no features), degs int64 [n] (the first m: kept edges per target),
+ * head int64 [3] = {m, E', error word}.  Error word: bit 0 a centre outside [0, n), bit 1 perm is not a permutation of 0 ... n - 1;
+ * the other outputs are then unspecified, every access stays in bounds.  The same input gives the same bytes. */
+size_t spg_sample_spg_workspace_bytes(long n, long E);
+int spg_sample_spg(const int32_t* ends, long E, long n, const int64_t* perm, const int64_t* centres, long n_centres, const int64_t* sizes,
+                   const float* feats, int F, int order, long minpts, long hardcutoff, int64_t* vids, int64_t* edges_out, int64_t* kept,
+                   float* feats_out, int64_t* degs, int64_t* head, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -186,6 +186,8 @@ SIGNATURES = {
     'spg_parsed_stats': (_i, [_p, _l, _i, _p, _p, _p, _p, _p, _sz, _p]),
     'spg_parsed_rows': (_i, [_i, _p, _l, _p, _i, _p, _p, _i, _p, _p, _p, _p, _l, _p, _i, _p, _p, _l, _p, _p, _p]),
     'spg_class_count': (_i, [_p, _i, _l, _i, _p, _p]),
+    'spg_sample_spg_workspace_bytes': (_sz, [_l, _l]),
+    'spg_sample_spg': (_i, [_p, _l, _l, _p, _p, _l, _p, _p, _i, _i, _l, _l, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     'spg_edge_features': (_i, [ctypes.POINTER(EdgeFeatureSpecs), _p, _l, _p, _p, _p, _p]),
     'spg_loader_random': (_i, [_p, _p, _p, _i, _i, _i, ctypes.c_uint64, ctypes.c_uint32, _i, ctypes.c_float, _i, ctypes.c_float, _i, _p, _p, _p, _p]),
     'spg_cross_entropy_fwd': (_i, [_p, _p, _p, _i, _i, ctypes.c_int64, _i, _p, _p, _p, _p]),

@@ -6,6 +6,7 @@ custom_dataset.py): `get_info` -> {node_feats, edge_feats, class_weights, classe
 The HDF5 readers need `h5py` (file I/O is outside the accelerated path); `register()` adds providers -- this is how the
 reference's "custom_dataset -- to write!" hook and the in-memory datasets of the tests and benchmarks plug in."""
 import functools
+import logging
 import os
 
 import numpy as np
@@ -90,7 +91,17 @@ def _loader_backend(args, root, store=None):
         if cache is None or cache._store is not store:
             cache = spg.DevicePointCache(store, torch.device('cuda', torch.cuda.current_device()))
             args._device_point_cache = cache
-        return {'device_cache': cache}
+        extra = {'device_cache': cache}
+        if getattr(args, 'spg_sample_device', 0):       # the sub-sampling on the scenes' resident graphs as well
+            graphs = getattr(args, '_device_graph_cache', None)
+            if graphs is None:
+                graphs = args._device_graph_cache = spg.DeviceGraphCache()
+            extra['device_graphs'] = graphs
+        return extra
+    if getattr(args, 'spg_sample_device', 0) and not getattr(args, '_warned_sample_device', False):
+        logging.warning('--spg_sample_device 1 ignored: it needs --cuda 1 --loader_device 1 (the sample is cut out of a graph resident '
+                        'in GPU memory and consumed by the device loader)')
+        args._warned_sample_device = True
     return {'store': store}
 
 

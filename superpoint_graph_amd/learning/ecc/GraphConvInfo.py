@@ -72,6 +72,9 @@ class GraphConvInfo(object):
         from ... import ops
         graphs = graphs if isinstance(graphs, (list, tuple)) else [graphs]
         dev = torch.device('cuda', torch.cuda.current_device()) if device is None else device
+        from .. import spg
+        if graphs and edge_feat_func is spg.cloud_edge_feats and all(isinstance(G, spg.DeviceSampledGraph) for G in graphs):
+            return self._set_batch_resident(graphs, dev, extras)
         p, edges = 0, []
         parts = [0]
         edgeattrs = defaultdict(list)
@@ -121,6 +124,34 @@ class GraphConvInfo(object):
         self._idxn, self._degrees_gpu = idxn, degs_gpu
         feats_d = ops.upload(feats, dev)
         self._edgefeats = ops.gather_rows(feats_d, perm) if idxn.numel() else feats_d
+        self._graph = ops.DeviceGraph(self._idxn, self._degrees_gpu)
+
+    def _set_batch_resident(self, graphs, dev, extras):
+        """set_batch_device over samples cut on the device (spg.DeviceSampledGraph): their edge lists (node offsets added) and
+        edge features are concatenated where they are, the host in-degrees come from the samples, and only `extras` are uploaded."""
+        from ... import ops
+        cur = torch.cuda.current_stream()
+        p, parts, edges, feats = 0, [0], [], []
+        for G in graphs:
+            G.edges.record_stream(cur); G.feats.record_stream(cur)      # (made on the sampler's stream, read on this one)
+            edges.append(G.edges + p if p else G.edges)
+            feats.append(G.feats)
+            p += G.vcount()
+            parts.append(p)
+        self._parts = parts
+        self._degrees = torch.cat([G.degs for G in graphs])
+        self._idxe, self._edge_indexes = None, None
+        edges_d = torch.cat(edges) if len(edges) > 1 else edges[0]
+        feats_d = torch.cat(feats) if len(feats) > 1 else feats[0]
+        extras = list(extras) if extras is not None else []
+        self.extras_dev = ops.upload_packed(extras, dev) if extras else []
+        built = ops.batch_graph_build(edges_d, feats_d, p, dev)
+        if built is not None:
+            self._idxn, self._degrees_gpu, self._edgefeats, self._graph, _err = built
+            return
+        idxn, degs_gpu, perm, _err = ops.set_batch(edges_d.contiguous(), p)
+        self._idxn, self._degrees_gpu = idxn, degs_gpu
+        self._edgefeats = ops.gather_rows(feats_d.contiguous(), perm)
         self._graph = ops.DeviceGraph(self._idxn, self._degrees_gpu)
 
     @classmethod

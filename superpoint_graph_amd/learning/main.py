@@ -101,6 +101,12 @@ def build_parser():
     a('--sp_decoder_config', default='[]', type=str, help='Size of the decoder : sp_embedding -> sp_class.')
     # HIP path
     a('--loader_device', default=1, type=int, help='Bool, build the superpoint clouds on the GPU from scenes resident in HBM')
+    a('--spg_sample_device', default=0, type=int,
+      help='Bool, run the neighbourhood sub-sampling of a training sample (permute_vertices, random_neighborhoods, k_big_enough) on '
+           'the GPU, on scene graphs resident in HBM (ops.sample_spg; index-exact with the host path, the random streams are drawn on '
+           'the host in the same order); evaluation serves the resident graph whole.  Only active with --cuda 1 --loader_device 1.  '
+           'Measured per sample at 1000 superpoints / 5000 superedges (profiles/spg_sample_bench.txt): 9.31 ms of host time on the host '
+           'path, 0.43 ms here (0.064 ms device time); default 0 until a training run has been measured with it')
     a('--batch_device', default=1, type=int,
       help='Bool, build the batched graph (edge ordering by target, edge-feature reordering, CSR) on the GPU in eccpc_collate; '
            'needs collation in the main process, i.e. it is only active together with --loader_device 1')

@@ -572,12 +572,111 @@ class DevicePointCache:
         return ent
 
 
-def loader(entry, train, args, db_path, test_seed_offset=0, store=None, device_cache=None):
+class DeviceSampledGraph:
+    """A loader sample's graph whose edges (i64 [E, 2], relabelled) and edge features (f32 [E, F]) are on the device and whose
+    in-degrees are on the host: what eccpc_collate(device_batch=True) -> GraphConvInfo.set_batch_device touches.  The igraph-like
+    accessors of the host construction (`get_edgelist`, `es`, `vs`) copy the sample to the host on first use."""
+
+    def __init__(self, n, edges, feats, degs):
+        self._n, self.edges, self.feats, self.degs = int(n), edges, feats, degs
+        self._host_graph = None
+
+    def vcount(self):
+        return self._n
+
+    def ecount(self):
+        return int(self.edges.shape[0])
+
+    def indegree(self, vs=None, loops=True):
+        return self.degs.tolist()
+
+    def _host(self):
+        if self._host_graph is None:
+            self._host_graph = SuperpointGraph(self._n, self.edges.cpu().numpy(), True, {'f': self.feats.cpu().numpy()})
+        return self._host_graph
+
+    def get_edgelist(self):
+        return self._host().get_edgelist()
+
+    @property
+    def es(self):
+        return self._host().es
+
+    @property
+    def vs(self):
+        return self._host().vs
+
+
+class DeviceGraphCache:
+    """Scenes' superpoint graphs resident in HBM, next to DevicePointCache: the first touch of a scene uploads its edges, its edge
+    features 'f' and its point counts 's' once (ops.ResidentSPG) and keeps the targets rows 't' on the host; afterwards a training
+    sample is cut out of the resident graph by kernels (ops.sample_spg) and only the permutation and the centres travel."""
+
+    def __init__(self):
+        self._scenes = {}
+
+    def scene(self, G, fname):
+        """-> (ResidentSPG, targets [n, ...] host array, in-degrees of the whole graph i64 [n] host tensor)"""
+        ent = self._scenes.get(fname)
+        if ent is None:
+            from .. import ops
+            n = G.vcount()
+            edges = getattr(G, '_edges', None)
+            edges = np.asarray(G.get_edgelist() if edges is None else edges, dtype=np.int64).reshape(-1, 2)
+            fast = getattr(G, 'edge_attribute_array', None)
+            feats = (fast('f') if fast is not None else np.asarray(G.es.get_attribute_values('f'))) if len(edges) else None
+            try:
+                sizes = np.asarray(G.vs['s'], dtype=np.int64)
+            except KeyError:
+                sizes = None
+            degs = torch.from_numpy(np.bincount(edges[:, 1], minlength=n).astype(np.int64))
+            ent = self._scenes[fname] = (ops.ResidentSPG(edges, feats, sizes, n), np.array(G.vs['t']), degs)
+        return ent
+
+
+def _sample_device_graph(G, fname, train, args, device_graphs):
+    """Step 1 of `loader` on a resident graph -> (DeviceSampledGraph or None for a sample without edges, vids, targets).  The
+    random streams are consumed as the host path consumes them: the shuffle, then the centres."""
+    import random
+    from .. import ops
+    rg, t, degs = device_graphs.scene(G, fname)
+    n = rg.n
+    perm = centres = None
+    if train:
+        if 0 < args.spg_augm_hardcutoff < n:
+            perm = list(range(n))
+            random.shuffle(perm)
+        if 0 < args.spg_augm_nneigh < n:
+            centres = random.sample(range(n), k=args.spg_augm_nneigh)
+    if perm is None and centres is None:             # evaluation, or nothing to cut: the whole resident graph, no kernel
+        if rg.E == 0:
+            return None, None, None
+        return DeviceSampledGraph(n, rg.edges, rg.feats, degs), list(range(n)), t
+    s = ops.sample_spg(rg, perm, centres, args.spg_augm_order, args.ptn_minpts, args.spg_augm_hardcutoff)
+    if s.E == 0:
+        return None, None, None
+    vids = s.vids.numpy()
+    return DeviceSampledGraph(s.n, s.edges, s.feats, s.degs), vids.tolist(), t[vids]
+
+
+def loader(entry, train, args, db_path, test_seed_offset=0, store=None, device_cache=None, device_graphs=None):
     """Prepares a (possibly sub-sampled) superpoint graph and its superpoint clouds (reference learning/spg.py:130-171).
     `store`: point store (default: the HDF5 files under db_path); `device_cache`: DevicePointCache -> the clouds are built
-    by ONE launch of the HIP loader kernel from the scene's resident ragged buffer and returned as CUDA tensors."""
+    by ONE launch of the HIP loader kernel from the scene's resident ragged buffer and returned as CUDA tensors;
+    `device_graphs`: DeviceGraphCache (with `device_cache`) -> the sub-sampling of step 1 runs on the GPU as well, on the scene's
+    resident graph, and the sample's graph is a DeviceSampledGraph."""
     import random
     G, fname = entry
+    if device_graphs is not None and device_cache is not None:
+        G, vids, targets = _sample_device_graph(G, fname, train, args, device_graphs)
+        if G is None:
+            return None, None, None, None, None, None
+        meta = ['{}.{:d}'.format(fname, v) for v in vids]
+        pts, off, index = device_cache.scene(fname)
+        rows = np.array([index[v] for v in vids], dtype=np.int64)
+        flag, clouds, diam = load_superpoints_device(args, pts, off[rows], vids, train, test_seed_offset,
+                                                     counts=off[rows + 1] - off[rows])
+        return targets, G, meta, flag, clouds, diam
     if train:                                        # 1) neighbourhood sub-sampling of the (permuted) graph, :134-144
         if 0 < args.spg_augm_hardcutoff < G.vcount():
             perm = list(range(G.vcount()))
