@@ -831,6 +831,41 @@ int spg_sample_spg(const int32_t* ends, long E, long n, const int64_t* perm, con
                    const float* feats, int F, int order, long minpts, long hardcutoff, int64_t* vids, int64_t* edges_out, int64_t* kept,
                    float* feats_out, int64_t* degs, int64_t* head, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- raw cloud text on the device (csrc/spg_text.hip; what the reference reads with pandas.read_csv in partition/provider.py:
+ * 185-217 read_s3dis_format, 250-303 read_semantic3d_format, 637-679 interpolate_labels_batch).
+ * text: device bytes [n_bytes], 16-byte aligned, 0 <= n_bytes <= 2^40.  A line ends at '\n'; one '\r' in front of it belongs to
+ * the terminator; lines that are empty in front of their terminator are skipped.  Two phases on the SAME workspace
+ * (spg_text_workspace_bytes(n_bytes)), because the number of lines sizes the outputs:
+ * spg_text_index -> head int64 [2] on the device = {lines, consumed}: consumed = the bytes up to and including the last '\n'; with
+ * final_block the bytes behind it count as a line too and consumed = n_bytes.
+ * spg_text_lines -> line_start int64 [n_lines], the offsets of the first byte of every line, ascending.
+ * spg_text_parse: every line has n_cols (<= SPG_TEXT_MAX_COLS) fields separated by exactly one space.  roles: HOST int [n_cols]:
+ * -1 = validated and dropped, 0 / 1 / 2 = x / y / z -> xyz float32 [n_lines, 3], 3 / 4 / 5 = r / g / b -> rgb uint8 [n_lines, 3],
+ * 6 -> label uint8 [n_lines]; an output no column feeds may be null.  A field is [+-] digits with at most one '.', at least one
+ * digit, at most 15 digits once leading zeros are dropped and at most 22 behind the '.'; its value is the digits as an integer
+ * divided once by 10^(digits behind the '.') in float64 (the correctly rounded float64), converted once to float32; zeros are +0.0.
+ * rgb and label fields are whole numbers in [0, 255].  Anything else is refused: error int64 [4] on the device = {the first
+ * refused line or -1, its SPG_TEXT_ERR_* code, the byte offset the code points at, the number of refused lines}; a refused line's
+ * outputs are zeros.  The first refusal met walking a line's bytes from the left counts, a field being judged at its end:
+ * EMPTY an empty field (at its offset), FIELDS more fields than n_cols (at the first byte of the field too many) or fewer (at
+ * the terminator), TOKEN a field outside the grammar, RANGE an rgb / label value (both at the field's first byte), BYTE a byte
+ * that is none of 0-9 . + - space (at it), LONG no terminator within SPG_TEXT_MAX_LINE bytes (at the first byte too many).
+ * No address is formed beyond n_bytes and no loop runs past a line's end, n_bytes or the cap. */
+#define SPG_TEXT_MAX_COLS 16
+#define SPG_TEXT_MAX_LINE 512
+enum { SPG_TEXT_ERR_FIELDS = 1, SPG_TEXT_ERR_EMPTY = 2, SPG_TEXT_ERR_BYTE = 3, SPG_TEXT_ERR_TOKEN = 4, SPG_TEXT_ERR_RANGE = 5,
+       SPG_TEXT_ERR_LONG = 6 };
+size_t spg_text_workspace_bytes(long n_bytes);
+int spg_text_index(const uint8_t* text, long n_bytes, int final_block, int64_t* head, void* workspace, size_t workspace_bytes,
+                   void* stream);
+int spg_text_lines(const uint8_t* text, long n_bytes, long n_lines, int64_t* line_start, void* workspace, size_t workspace_bytes,
+                   void* stream);
+int spg_text_parse(const uint8_t* text, long n_bytes, const int64_t* line_start, long n_lines, int n_cols, const int* roles,
+                   float* xyz, uint8_t* rgb, uint8_t* label, int64_t* error, void* stream);
+/* test helper (host only): 0 = the bytes of text a workgroup of the index kernels reads with its 16-byte loads (tiles start at
+ * offset 0), 1 = SPG_TEXT_MAX_LINE; -1 otherwise */
+int spg_text_debug_layout(int which);
+
 #ifdef __cplusplus
 }
 #endif

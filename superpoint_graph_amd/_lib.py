@@ -188,6 +188,11 @@ SIGNATURES = {
     'spg_class_count': (_i, [_p, _i, _l, _i, _p, _p]),
     'spg_sample_spg_workspace_bytes': (_sz, [_l, _l]),
     'spg_sample_spg': (_i, [_p, _l, _l, _p, _p, _l, _p, _p, _i, _i, _l, _l, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    'spg_text_workspace_bytes': (_sz, [_l]),
+    'spg_text_index': (_i, [_p, _l, _i, _p, _p, _sz, _p]),
+    'spg_text_lines': (_i, [_p, _l, _l, _p, _p, _sz, _p]),
+    'spg_text_parse': (_i, [_p, _l, _p, _l, _i, ctypes.POINTER(_i), _p, _p, _p, _p, _p]),
+    'spg_text_debug_layout': (_i, [_i]),
     'spg_edge_features': (_i, [ctypes.POINTER(EdgeFeatureSpecs), _p, _l, _p, _p, _p, _p]),
     'spg_loader_random': (_i, [_p, _p, _p, _i, _i, _i, ctypes.c_uint64, ctypes.c_uint32, _i, ctypes.c_float, _i, ctypes.c_float, _i, _p, _p, _p, _p]),
     'spg_cross_entropy_fwd': (_i, [_p, _p, _p, _i, _i, ctypes.c_int64, _i, _p, _p, _p, _p]),
