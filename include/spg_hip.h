@@ -866,6 +866,32 @@ int spg_text_parse(const uint8_t* text, long n_bytes, const int64_t* line_start,
  * offset 0), 1 = SPG_TEXT_MAX_LINE; -1 otherwise */
 int spg_text_debug_layout(int which);
 
+/* ---- l0 cut pursuit (csrc/spg_cutpursuit.hip).  rowptr / inc / ends of spg_edgegraph_build.
+ * spg_mincut: cap int64 [E], cost0 / cost1 int64 [n], every value in [0, 2^28) -> label uint8 [n] minimising sum_v cost_label(v) +
+ * sum_e cap_e [label_u != label_v]; among the minimisers the one with the fewest ones (label 1 = the vertices that reach the sink in
+ * the residual graph of a maximum preflow; source -> v has capacity cost1, v -> sink cost0, every edge cap both ways; self-loops and
+ * zero capacities are inert, parallel edges add up).  Synchronous push-relabel in pulses of three launches with a breadth-first
+ * global relabel every 16 pulses; integer arithmetic only, the result and the pulse count do not depend on scheduling.  The stream
+ * is synchronised once per 16 pulses and once per 16 breadth-first levels.  info_host: HOST int64 [4] = {error bits: 1 = a value
+ * outside [0, 2^28) (nothing was run), 2 = still active after max_pulses pulses (label is not the answer); pulses used; kernel
+ * launches; breadth-first levels}.
+ * spg_cp_accumulate: W int64 [K] = sum mq, S int64 [K, D] = sum mq * q over the vertices with 0 <= key < K (zeroed here; int64
+ * atomics, exact in any order).  q int32 [n, D], mq int32 [n], key int32 [n].
+ * spg_cp_dist: out float64 [n] = sum_d (q[v, d] - C[key[v], d])^2, left to right, every product and sum rounded on its own (no
+ * contraction); 0 where key is outside [0, K).  C float64 [K, D].
+ * spg_cp_farthest: per key the largest dist among the vertices with mq > 0 (best_bits int64 [K]: the float64's bits, 0 if none) and
+ * the first vertex that has it (idx int32 [K], n if none). */
+#define SPG_CP_MAX_D 32
+size_t spg_mincut_workspace_bytes(long n, long E);
+int spg_mincut(const int32_t* rowptr, const uint32_t* inc, const int32_t* ends, long E, long n, const int64_t* cap,
+               const int64_t* cost0, const int64_t* cost1, long max_pulses, uint8_t* label, int64_t* info_host, void* workspace,
+               size_t workspace_bytes, void* stream);
+int spg_cp_accumulate(const int32_t* key, const int32_t* mq, const int32_t* q, long n, int D, long K, int64_t* W, int64_t* S,
+                      void* stream);
+int spg_cp_dist(const int32_t* q, const int32_t* key, const double* C, long n, int D, long K, double* out, void* stream);
+int spg_cp_farthest(const double* dist, const int32_t* key, const int32_t* mq, long n, long K, int64_t* best_bits, int32_t* idx,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

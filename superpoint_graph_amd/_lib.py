@@ -193,6 +193,11 @@ SIGNATURES = {
     'spg_text_lines': (_i, [_p, _l, _l, _p, _p, _sz, _p]),
     'spg_text_parse': (_i, [_p, _l, _p, _l, _i, ctypes.POINTER(_i), _p, _p, _p, _p, _p]),
     'spg_text_debug_layout': (_i, [_i]),
+    'spg_mincut_workspace_bytes': (_sz, [_l, _l]),
+    'spg_mincut': (_i, [_p, _p, _p, _l, _l, _p, _p, _p, _l, _p, _p, _p, _sz, _p]),
+    'spg_cp_accumulate': (_i, [_p, _p, _p, _l, _i, _l, _p, _p, _p]),
+    'spg_cp_dist': (_i, [_p, _p, _p, _l, _i, _l, _p, _p]),
+    'spg_cp_farthest': (_i, [_p, _p, _p, _l, _l, _p, _p, _p]),
     'spg_edge_features': (_i, [ctypes.POINTER(EdgeFeatureSpecs), _p, _l, _p, _p, _p, _p]),
     'spg_loader_random': (_i, [_p, _p, _p, _i, _i, _i, ctypes.c_uint64, ctypes.c_uint32, _i, ctypes.c_float, _i, ctypes.c_float, _i, _p, _p, _p, _p]),
     'spg_cross_entropy_fwd': (_i, [_p, _p, _p, _i, _i, ctypes.c_int64, _i, _p, _p, _p, _p]),

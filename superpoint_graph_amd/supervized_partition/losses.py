@@ -6,8 +6,10 @@ ops.crosspartition_weights, ops.seal_weights, ops.component_mode, ops.relax_edge
 over the vertices without atomics (deterministic), the cross-partition weights are a device connected-components pass and a
 sort, the SEAL weights a sort of (component, object) pairs and one launch over the edges.
 
-What is not here: cut pursuit (`libcp`, losses.py:67-89 compute_partition).  The predicted partition is an INPUT:
-`compute_weight_loss(..., partition=(pred_components, pred_in_component))` takes what the caller's own cut pursuit returned.
+The predicted partition (losses.py:67-89 compute_partition) comes from the device cut pursuit of partition/libcp.py
+(ops.cut_pursuit, UNPINNED against libcp: DESIGN.md section 4.11j): `compute_weight_loss(..., partition='device')` computes it,
+`partition=(pred_components, pred_in_component)` takes what the caller's own cut pursuit returned, and without either the
+functions that need a partition refuse as before.
 `relax_edge_binary` reproduces what the reference's function computes, including what its integer indexing does (see
 ops.relax_edges).  No CPU path."""
 from __future__ import annotations
@@ -163,10 +165,34 @@ def relax_edge_binary(edg_binary, edg_source, edg_target, n_ver, tolerance):
     return out.cpu().numpy()
 
 
+def compute_partition(args, embeddings, edg_source, edg_target, diff, xyz=0, device=False):
+    """losses.py:67-89 -> (pred_components, pred_in_component) of libcp.cutpursuit on the embeddings (and spatial_emb * xyz when
+    args.spatial_emb > 0) with the reference's edge weights, regularisation reg_strength / (4 k_nn_adj), cutoff CP_cutoff and
+    decay 0.7.  numpy as the reference returns it; device=True: device tensors.  edg_source may be an EdgeGraph."""
+    from ..partition import libcp
+    _require_gpu(embeddings, 'embeddings'); _require_gpu(diff, 'diff')
+    dev = embeddings.device
+    E = int(diff.shape[0])
+    edge_weight = torch.ones(E, dtype=torch.float32, device=dev)
+    if args.edge_weight_threshold > 0:
+        edge_weight[diff.detach() > 1] = args.edge_weight_threshold
+    if args.edge_weight_threshold < 0:
+        # (a float32 division by a tensor: dividing by a host scalar multiplies by its reciprocal)
+        edge_weight = torch.exp(diff.detach().float() * args.edge_weight_threshold) / \
+            torch.tensor(np.exp(args.edge_weight_threshold), dtype=torch.float32, device=dev)
+    ver_value = embeddings.detach().float()
+    if args.spatial_emb > 0:
+        pos = xyz if torch.is_tensor(xyz) else torch.from_numpy(np.ascontiguousarray(xyz))
+        ver_value = torch.cat([ver_value, args.spatial_emb * pos.to(device=dev, dtype=torch.float32)], 1)
+    g = _graph(edg_source, edg_target, int(embeddings.shape[0]))
+    return libcp.cutpursuit(ver_value.contiguous(), g, None, edge_weight, args.reg_strength / (4 * args.k_nn_adj), cutoff=args.CP_cutoff,
+                            spatial=int(args.spatial_emb > 0), weight_decay=0.7, device=device)
+
+
 def compute_weight_loss(args, embeddings, objects, edg_source, edg_target, is_transition, diff, return_partition, xyz=0, partition=None):
-    """losses.py:91-117.  partition = (pred_components, pred_in_component) of the caller's cut pursuit (needed by
-    loss_weight 'crosspartition' and 'seal' and by return_partition; 'seal' without it raises NotImplementedError).  -> weights float32 [E] on the device [, pred_components,
-    pred_in_component]."""
+    """losses.py:91-117.  partition = (pred_components, pred_in_component) of the caller's cut pursuit, or 'device': compute_partition
+    on the device (a partition is needed by loss_weight 'crosspartition' and 'seal' and by return_partition; 'seal' without it raises
+    NotImplementedError).  -> weights float32 [E] on the device [, pred_components, pred_in_component]."""
     if args.loss_weight == 'seal' and partition is None:
         raise NotImplementedError(_NO_LIBCP % "loss_weight 'seal'")
     if args.loss_weight not in ('none', 'proportional', 'crosspartition', 'seal'):
@@ -176,6 +202,11 @@ def compute_weight_loss(args, embeddings, objects, edg_source, edg_target, is_tr
     _require_gpu(embeddings, 'embeddings'); _require_gpu(is_transition, 'is_transition')
     dev = embeddings.device
     E = int(is_transition.shape[0])
+    if isinstance(partition, str):
+        if partition != 'device':
+            raise ValueError(f"partition must be (pred_components, pred_in_component) or 'device', got {partition!r}")
+        needed = args.loss_weight in ('seal', 'crosspartition') or return_partition
+        partition = compute_partition(args, embeddings, edg_source, edg_target, diff, xyz, device=True) if needed else None
     if args.loss_weight == 'none':
         weights_loss = torch.ones(E, dtype=torch.float32, device=dev)
     elif args.loss_weight == 'proportional':

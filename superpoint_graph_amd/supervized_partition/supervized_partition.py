@@ -5,8 +5,8 @@ transformer `model.stn` and a PointNet without inner transformer `model.ptn`, ev
 `learning.pointnet.LocalCloudEmbedder`.  The two flags that reach only this embedder are honoured: `ptn_norm`
 ('batch' | 'layer' | 'group') and `ptn_n_group`; module order and state_dict keys are the reference's, so its checkpoints load
 with strict=True.  For the hand-crafted vertex values (ver_value 'geof' / 'geofrgb', learned_embeddings 0: :423-428) the model is
-the reference's single placeholder parameter.  The training loop itself is not part of this package: it needs cut pursuit, which
-stays an input."""
+the reference's single placeholder parameter.  The training loop itself is not part of this package; what it calls per step is
+(losses.py, and cut pursuit through compute_weight_loss(..., partition='device'))."""
 import torch
 import torch.nn as nn
 
