@@ -24,6 +24,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
+from .ops._core import _ptr_array, _req, _stream
 from .flat import mark_direct_write
 
 
@@ -56,7 +57,7 @@ class FusedStep:
         self.ptn = model.ptn
         self.conv, self.fc = list(model.ecc.children())
         # (validated like every other device operand: a CPU / other-GPU tensor here would reach the kernels as a wild pointer)
-        self.class_weights = None if class_weights is None else ops._req(class_weights.detach().float().contiguous(), torch.float32, 'class_weights')
+        self.class_weights = None if class_weights is None else _req(class_weights.detach().float().contiguous(), torch.float32, 'class_weights')
         if self.class_weights is not None and self.class_weights.numel() != list(model.ecc.children())[1].out_features:
             raise ValueError('class_weights: one weight per class expected')
         self.mean = reduction == 'mean'
@@ -95,8 +96,8 @@ class FusedStep:
         ecc_grads = grads_of(ecc_groups[:nf], 4) + grads_of(ecc_groups[nf:], 6)
         keep += ptn_grads + ecc_grads
         self._plan = dict(npts=npts, ptn_cfg=ptn_cfg, ecc_cfg=ecc_cfg,
-                          ptn_params=ops._ptr_array([t for g in pg for t in g]), ptn_grads=ops._ptr_array(ptn_grads),
-                          ecc_params=ops._ptr_array([t for g in ecc_groups for t in g]), ecc_grads=ops._ptr_array(ecc_grads),
+                          ptn_params=_ptr_array([t for g in pg for t in g]), ptn_grads=_ptr_array(ptn_grads),
+                          ecc_params=_ptr_array([t for g in ecc_groups for t in g]), ecc_grads=_ptr_array(ecc_grads),
                           keep=keep, nf=int(ptn_cfg.fc[ptn_cfg.n_fc - 1]),
                           nout=int(ecc_cfg.nc * (ecc_cfg.nrepeats + 1) if ecc_cfg.cat_all else ecc_cfg.nc))
         return self._plan
@@ -138,14 +139,14 @@ class FusedStep:
         idx_valid, slot_of_row = stage_flags(clouds_flag)
         clouds = ops.upload(clouds, dev) if not clouds.is_cuda else clouds
         clouds_global = ops.upload(clouds_global, dev) if not clouds_global.is_cuda else clouds_global
-        clouds = ops._req(clouds.contiguous(), torch.float32, 'clouds')
+        clouds = _req(clouds.contiguous(), torch.float32, 'clouds')
         B, N = int(clouds.shape[0]), int(clouds_flag.shape[0])
         if B <= 1:
             raise ValueError(f'Expected more than 1 value per channel when training, got input size [{B}, C]')
         plan = self._tables(int(clouds.shape[2]))
         if clouds.shape[1] != plan['ptn_cfg'].nfeat:
             raise ValueError('clouds: wrong number of point features')
-        clouds_global = ops._req(clouds_global.reshape(B, -1).contiguous(), torch.float32, 'clouds_global')
+        clouds_global = _req(clouds_global.reshape(B, -1).contiguous(), torch.float32, 'clouds_global')
         idxn, idxe, degs, degs_gpu, edgefeats = gc_info.get_buffers()
         if idxe is not None:
             raise NotImplementedError('filter sharing (idxe) is not supported by the fused RNN-ECC path')
@@ -153,10 +154,10 @@ class FusedStep:
         E = int(graph.E)
         if graph.N != N:
             raise ValueError(f'the batched graph has {graph.N} nodes, clouds_flag has {N} rows')
-        edgefeats = ops._req(edgefeats.contiguous().float(), torch.float32, 'edgefeats')
+        edgefeats = _req(edgefeats.contiguous().float(), torch.float32, 'edgefeats')
         if plan['ecc_cfg'].bnidx >= 0 and E == 1:
             raise ValueError('Expected more than 1 value per channel when training (filter-network BatchNorm over one edge)')
-        target = ops._req(target.contiguous(), torch.int64, 'target')
+        target = _req(target.contiguous(), torch.int64, 'target')
         ecc_cfg, _ = conv._cfg_for(gc_info, N)              # (+ the batch's scene boundaries for graphs above one round)
         b = self._buffers(plan, B, N, E, dev, ecc_cfg)
         C = fc.out_features
@@ -187,7 +188,7 @@ class FusedStep:
         # the statistics slots inside ptn_ws are zero after every successful step on these buffers (include/spg_hip.h)
         a.ptn_slots_clean = 1 if b.get('slots_clean') else 0
         b['slots_clean'] = False
-        _lib.check(_lib.lib().spg_train_step(ctypes.byref(a), ops._stream()), 'spg_train_step')
+        _lib.check(_lib.lib().spg_train_step(ctypes.byref(a), _stream()), 'spg_train_step')
         b['slots_clean'] = True
         # module-level bookkeeping the C call does not do -- only once the call has succeeded (a refused step must not advance
         # the BatchNorm batch counters or mark gradients as written)
@@ -214,14 +215,14 @@ class FusedStep:
         idx_valid, slot_of_row = stage_flags(clouds_flag)
         clouds = ops.upload(clouds, dev) if not clouds.is_cuda else clouds
         clouds_global = ops.upload(clouds_global, dev) if not clouds_global.is_cuda else clouds_global
-        clouds = ops._req(clouds.contiguous(), torch.float32, 'clouds')
+        clouds = _req(clouds.contiguous(), torch.float32, 'clouds')
         B, N = int(clouds.shape[0]), int(clouds_flag.shape[0])
         if B < 1:
             raise ValueError('no embeddable superpoint in the batch')
         plan = self._tables(int(clouds.shape[2]))
         if clouds.shape[1] != plan['ptn_cfg'].nfeat:
             raise ValueError('clouds: wrong number of point features')
-        clouds_global = ops._req(clouds_global.reshape(B, -1).contiguous(), torch.float32, 'clouds_global')
+        clouds_global = _req(clouds_global.reshape(B, -1).contiguous(), torch.float32, 'clouds_global')
         idxn, idxe, degs, degs_gpu, edgefeats = gc_info.get_buffers()
         if idxe is not None:
             raise NotImplementedError('filter sharing (idxe) is not supported by the fused RNN-ECC path')
@@ -229,7 +230,7 @@ class FusedStep:
         E = int(graph.E)
         if graph.N != N:
             raise ValueError(f'the batched graph has {graph.N} nodes, clouds_flag has {N} rows')
-        edgefeats = ops._req(edgefeats.contiguous().float(), torch.float32, 'edgefeats')
+        edgefeats = _req(edgefeats.contiguous().float(), torch.float32, 'edgefeats')
         ecc_cfg, _ = conv._cfg_for(gc_info, N)
         key = ('infer', B, N, E, dev)
         b = self._bufs.get(key)
@@ -258,7 +259,7 @@ class FusedStep:
         a.ecc_params, a.ecc_ws, a.ecc_out = plan['ecc_params'], b['ecc_ws'].data_ptr(), b['ecc_out'].data_ptr()
         a.nout, a.n_classes = plan['nout'], C
         a.cls_W, a.cls_b, a.logits = fc.weight.data_ptr(), None if fc.bias is None else fc.bias.data_ptr(), logits.data_ptr()
-        _lib.check(_lib.lib().spg_infer_step(ctypes.byref(a), ops._stream()), 'spg_infer_step')
+        _lib.check(_lib.lib().spg_infer_step(ctypes.byref(a), _stream()), 'spg_infer_step')
         return logits
 
     def debug_states(self):

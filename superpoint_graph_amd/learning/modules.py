@@ -2,7 +2,7 @@
 import torch
 import torch.nn as nn
 
-from .. import ops
+from .. import _lib, ops
 
 
 class GRUCellEx(nn.GRUCell):
@@ -244,7 +244,7 @@ class RNNGraphConvModule(nn.Module):
         a forward travels with its saved state to the backward."""
         cfg, groups = self._cfg_and_groups()
         parts = getattr(gci, '_parts', None)
-        if parts is None or n_nodes <= 2048 or len(parts) - 1 > ops._lib.SPG_MAX_PARTS or len(parts) < 3:
+        if parts is None or n_nodes <= 2048 or len(parts) - 1 > _lib.SPG_MAX_PARTS or len(parts) < 3:
             return cfg, groups
         key = tuple(parts)
         cache = self.__dict__.setdefault('_cfg_parts_cache', {})

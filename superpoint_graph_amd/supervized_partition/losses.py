@@ -19,6 +19,7 @@ import torch
 
 from .. import ops
 from ..ops import EdgeGraph
+from ..ops.edges import _loss_codes
 
 _NO_LIBCP = ("%s needs the predicted partition, which the reference gets from cut pursuit (libcp.cutpursuit, losses.py:82); "
              "libcp is not part of this package: run your own cut pursuit and pass partition=(pred_components, pred_in_component)")
@@ -88,7 +89,7 @@ def compute_dist(embeddings, edg_source, edg_target, dist_type):
 
 def compute_loss(args, diff, is_transition, weights_loss):
     """losses.py:44-64 -> (loss1, loss2), float32 scalars on the device, differentiable wrt diff."""
-    ops._loss_codes(args.loss)
+    _loss_codes(args.loss)
     _require_gpu(diff, 'diff')
     return ops.edge_loss(diff, _edge_tensor(is_transition, diff.device), _edge_tensor(weights_loss, diff.device), args.loss,
                          args.dist_type)

@@ -27,6 +27,7 @@ sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import cloud_text_cases as C  # noqa: E402
 import cloud_text_restatement as R  # noqa: E402
 from superpoint_graph_amd import ops  # noqa: E402
+from superpoint_graph_amd.ops.text import _text_roles  # noqa: E402
 from superpoint_graph_amd._lib import CSRC, check, lib  # noqa: E402
 
 HBM_COPY = 6.29e12            # bytes/s, the measured float4 copy of an MI355X (8.0e12 on paper)
@@ -59,7 +60,7 @@ def kernels(text, reps, say):
     xyz = torch.empty(n, 3, dtype=torch.float32, device=dev)
     rgb = torch.empty(n, 3, dtype=torch.uint8, device=dev)
     err = torch.empty(4, dtype=torch.int64, device=dev)
-    roles = ops._text_roles(7, (0, 1, 2), (4, 5, 6), None)
+    roles = _text_roles(7, (0, 1, 2), (4, 5, 6), None)
     parse = lambda: check(L.spg_text_parse(text.data_ptr(), nb, line_start.data_ptr(), n, 7, roles, xyz.data_ptr(), rgb.data_ptr(),
                                            None, err.data_ptr(), st))
     t_parse, all_parse = events(parse, reps)

@@ -1,6 +1,7 @@
 """Writes tests/golden/part_reduce_parent.npz: the bits of the partition units' fixed-order reductions (tests/part_reduce_cases.py)
 as the commit BEFORE they moved into csrc/spg_part.h computes them on an MI355X.  Run it on a checkout and build of that commit --
-the whole tree, ops.py included -- never on a later one: the file is the record that the move changed no bit.
+the whole tree, its Python wrappers (then one file, now the superpoint_graph_amd/ops package) included -- never on a later one: the
+file is the record that the move changed no bit.
 
   <case>/<field>    what part_reduce_cases.CASES[case] returns: small results whole, per-point arrays as SHA-256 digests
   parent_commit     the commit the record was taken on (--commit, default: git rev-parse HEAD)

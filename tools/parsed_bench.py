@@ -21,6 +21,7 @@ sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import parsed_cases as C  # noqa: E402
 import parsed_restatement as R  # noqa: E402
 from superpoint_graph_amd import ops  # noqa: E402
+from superpoint_graph_amd.ops._core import _ptr, _stream  # noqa: E402
 from superpoint_graph_amd.learning import parsed  # noqa: E402
 
 
@@ -58,7 +59,7 @@ def main():
         return p, (time.perf_counter() - t0) * 1e3
 
     L = ops.lib()
-    P, S = ops._ptr, ops._stream
+    P, S = _ptr, _stream
     s32, s64, cen = ops.scene_stats(xyz, True)
     off_d = torch.from_numpy(off).cuda()
     rows = int(off[-1])

@@ -18,7 +18,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import structure_restatement as R  # noqa: E402
 from superpoint_graph_amd import _lib, ops  # noqa: E402
-from superpoint_graph_amd.ops import _ptr, _stream  # noqa: E402
+from superpoint_graph_amd.ops._core import _ptr, _stream  # noqa: E402
 from superpoint_graph_amd.supervized_partition import graph_processing as GP  # noqa: E402
 
 K_LOCAL, K_ADJ, N_LABELS, VOXEL = 20, 5, 13, 0.03
