@@ -15,6 +15,8 @@ from typing import Optional
 import torch
 import torch.distributed as dist
 
+from . import _lib
+
 
 class FlatParameters:
     def __init__(self, model: torch.nn.Module, lazy_zero: bool = False, host_counters: bool = False):
@@ -83,7 +85,6 @@ class FlatParameters:
         of the whole arena in ONE HIP launch (spg_adam_clamp_step).  The moments live in this object.
         grad_div: [1] device tensor; every gradient is divided by it first (`allreduce_sums` leaves the data-parallel
         normaliser in `self.normaliser`)."""
-        from . import _lib
         if not hasattr(self, '_m'):
             self._m = torch.zeros_like(self.flat.data)
             self._v = torch.zeros_like(self.flat.data)
@@ -158,7 +159,6 @@ class FlatParameters:
         [gradients | w_r | loss_r] is summed over the ranks in place; the division by sum_r w_r happens inside the clamp + Adam
         launch (adam_step(grad_div=self.normaliser)).  World size 1 (or no process group): the same code without the
         collective -- the result is the single-process gradient of the mean-reduced loss."""
-        from . import _lib
         self._resolve_stale()
         self._gbuf[self.numel:self.numel + 1].copy_(weight.reshape(1), non_blocking=True)
         if loss_sum is not None:
@@ -219,7 +219,6 @@ class FlatParameters:
     def allreduce(self, local_weight: float = 1.0, group=None, prescaled: bool = False):
         """Weighted data-parallel mean of the gradients (see superpoint_graph_amd/dist.py), in place on the arena.
         prescaled: the loss was already multiplied by local_weight (synchronised-BatchNorm mode)."""
-        from . import _lib
         self._resolve_stale()
         native = _lib.lib().spg_rccl_world_size()           # the library's own communicator (dist.init_native_rccl)
         if native <= 1 and not (dist.is_initialized() and dist.get_world_size(group) > 1):
@@ -238,13 +237,9 @@ class FlatParameters:
 
 
 def _direct_writer(m):
-    """Module classes whose HIP backward WRITES the gradient views of all parameters below them (PointNet incl. its STN,
-    a stand-alone STNkD, the RNN-ECC module incl. filter network and cell, HipLinear on the kernel path)."""
-    from .learning.modules import HipLinear, RNNGraphConvModule
-    from .learning.pointnet import PointNet, STNkD
-    if isinstance(m, HipLinear):
-        return m._kernel_shape_ok()
-    return isinstance(m, (PointNet, STNkD, RNNGraphConvModule))
+    """Modules whose HIP backward WRITES the gradient views of all parameters below them say so in `_spg_kernel_grads` (PointNet
+    incl. its STN, a stand-alone STNkD, the RNN-ECC module incl. filter network and cell, HipLinear on the kernel path)."""
+    return bool(getattr(m, '_spg_kernel_grads', False))
 
 
 def prepare_autograd_fallback(module):

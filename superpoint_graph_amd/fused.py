@@ -19,20 +19,29 @@ returned loss / logits are detached; anything outside `supports(model)` must use
 from __future__ import annotations
 
 import ctypes
+import types
 
 import torch
-import torch.nn as nn
 
 from . import _lib, ops
-from .ops._core import _ptr_array, _req, _stream
 from .flat import mark_direct_write
+from .learning._layers import advance_batch_counters, grad_targets
+from .learning.modules import HipLinear, RNNGraphConvModule
+from .learning.pointnet import PointNet, stage_flags
+from .ops._core import _ptr_array, _req, _stream
+from .ops.model import rows6
+
+
+def _workspaces(dev, *sizes):
+    """One uint8 tensor per workspace query of the library (0: the query failed)."""
+    if min(sizes) == 0:
+        raise RuntimeError('workspace query failed: ' + _lib.lib().spg_last_error().decode())
+    return [torch.empty(max(int(n), 256), dtype=torch.uint8, device=dev) for n in sizes]
 
 
 def supports(model) -> bool:
     """True for `model.ptn` = PointNet (inner STN or none) and `model.ecc` = GraphNetwork of exactly one recurrent graph
     convolution followed by one linear layer that the HIP kernels serve."""
-    from .learning.modules import HipLinear, RNNGraphConvModule
-    from .learning.pointnet import PointNet
     ptn, ecc = getattr(model, 'ptn', None), getattr(model, 'ecc', None)
     if not isinstance(ptn, PointNet) or ecc is None:
         return False
@@ -70,118 +79,108 @@ class FusedStep:
     def _tables(self, npts):
         if self._plan is not None and self._plan['npts'] == npts:
             return self._plan
-        ptn, conv, fc = self.ptn, self.conv, self.fc
-        ptn_cfg = ptn._cfg(npts)
-        ecc_cfg, ecc_groups = conv._cfg_and_groups()
-        pg = ptn._groups_tensors()
-
-        def grads_of(groups, nparam):
-            rows = []
-            for g in groups:
-                has_bn = nparam == 4 and g[2] is not None
-                row = []
-                for k in range(6):
-                    t = g[k] if k < nparam else None
-                    if t is None or (has_bn and k == 1):      # a bias in front of train-mode BatchNorm: zero gradient, never written
-                        row.append(None)
-                    else:
-                        if t.grad is None or not t.grad.is_contiguous():
-                            raise RuntimeError('FusedStep: a parameter has no contiguous .grad view into the gradient arena')
-                        row.append(t.grad)
-                rows += row
-            return rows
-        nf = ecc_cfg.n_fnet
-        keep = [t for g in pg for t in g] + [t for g in ecc_groups for t in g]
-        ptn_grads = grads_of(pg, 4)
-        ecc_grads = grads_of(ecc_groups[:nf], 4) + grads_of(ecc_groups[nf:], 6)
-        keep += ptn_grads + ecc_grads
+        ptn_cfg = self.ptn._cfg(npts)
+        ecc_cfg, ecc_rows = self.conv._cfg_and_groups()
+        tables = []      # parameters and gradient targets of PointNet, then of the RNN-ECC module: six pointers per row
+        for rows in (self.ptn._groups_tensors(), ecc_rows):
+            tables += [[t for r in rows for t in r], [t for r in rows6(grad_targets(rows, strict=True)) for t in r]]
         self._plan = dict(npts=npts, ptn_cfg=ptn_cfg, ecc_cfg=ecc_cfg,
-                          ptn_params=_ptr_array([t for g in pg for t in g]), ptn_grads=_ptr_array(ptn_grads),
-                          ecc_params=_ptr_array([t for g in ecc_groups for t in g]), ecc_grads=_ptr_array(ecc_grads),
-                          keep=keep, nf=int(ptn_cfg.fc[ptn_cfg.n_fc - 1]),
+                          ptn_params=_ptr_array(tables[0]), ptn_grads=_ptr_array(tables[1]),
+                          ecc_params=_ptr_array(tables[2]), ecc_grads=_ptr_array(tables[3]),
+                          keep=tables, nf=int(ptn_cfg.fc[ptn_cfg.n_fc - 1]),
                           nout=int(ecc_cfg.nc * (ecc_cfg.nrepeats + 1) if ecc_cfg.cat_all else ecc_cfg.nc))
         return self._plan
 
-    def _buffers(self, plan, B, N, E, dev, ecc_cfg):
+    def _buffers(self, key, make):
         """Workspaces and activations of one step, re-used from step to step while the sizes stay the same (one stream: the
         next step overwrites them only after this one has consumed them)."""
-        # (npts: the PointNet plan -- hence the workspace layout and the statistics slots -- depends on the points per cloud)
-        key = (B, N, E, dev, plan['npts'], tuple(ecc_cfg.part_ptr[:ecc_cfg.n_parts + 1]) if ecc_cfg.n_parts > 0 else ())
         b = self._bufs.get(key)
-        if b is not None:
-            return b
-        L = _lib.lib()
-        pc, ec = ctypes.byref(plan['ptn_cfg']), ctypes.byref(ecc_cfg)
-        nf, nout, C = plan['nf'], plan['nout'], self.fc.out_features
-        u8 = lambda n: torch.empty(max(int(n), 256), dtype=torch.uint8, device=dev)
-        f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
-        sizes = (L.spg_pointnet_workspace_bytes(pc, B, 1), L.spg_pointnet_bwd_workspace_bytes(pc, B),
-                 L.spg_eccrnn_workspace_bytes(ec, N, E, 1), L.spg_eccrnn_bwd_workspace_bytes(ec, N, E))
-        if min(sizes) == 0:
-            raise RuntimeError('workspace query failed: ' + L.spg_last_error().decode())
-        b = dict(ptn_ws=u8(sizes[0]), ptn_bwd_ws=u8(sizes[1]), ecc_ws=u8(sizes[2]), ecc_bwd_ws=u8(sizes[3]),
-                 emb=f32(B, nf), grad_emb=f32(B, nf), desc=f32(N, nf), grad_desc=f32(N, nf), ecc_out=f32(N, nout), grad_ecc_out=f32(N, nout),
-                 cls_work=f32(max(1, L.spg_linear_wgrad_bias_work_floats(N, C, nout))), grad_logits=f32(N, C))
-        if len(self._bufs) >= 4:       # a few batch shapes at most stay cached (training batches vary in size)
-            self._bufs.pop(next(iter(self._bufs)))
-        self._bufs[key] = b
+        if b is None:
+            b = make()
+            if len(self._bufs) >= 4:       # a few batch shapes at most stay cached (training batches vary in size)
+                self._bufs.pop(next(iter(self._bufs)))
+            self._bufs[key] = b
         return b
+
+    def _stage(self, training, clouds_flag, clouds, clouds_global, gc_info, buffers):
+        """Stages and validates the inputs of a step and fills the StepArgs fields that training and inference share.
+        buffers(s, pc, ec) -> the step's cached buffers.  -> (StepArgs, s): `s` holds what the caller still needs, and every
+        tensor the library call reads -- it must stay alive until that call has been enqueued."""
+        conv, fc = self.conv, self.fc
+        s = types.SimpleNamespace(dev=torch.device('cuda', torch.cuda.current_device()))
+        s.idx_valid, s.slot_of_row = stage_flags(clouds_flag)
+        clouds = ops.upload(clouds, s.dev) if not clouds.is_cuda else clouds
+        clouds_global = ops.upload(clouds_global, s.dev) if not clouds_global.is_cuda else clouds_global
+        s.clouds = clouds = _req(clouds.contiguous(), torch.float32, 'clouds')
+        s.B, s.N = B, N = int(clouds.shape[0]), int(clouds_flag.shape[0])
+        if training and B <= 1:
+            raise ValueError(f'Expected more than 1 value per channel when training, got input size [{B}, C]')
+        if B < 1:
+            raise ValueError('no embeddable superpoint in the batch')
+        s.plan = plan = self._tables(int(clouds.shape[2]))
+        if clouds.shape[1] != plan['ptn_cfg'].nfeat:
+            raise ValueError('clouds: wrong number of point features')
+        s.clouds_global = clouds_global = _req(clouds_global.reshape(B, -1).contiguous(), torch.float32, 'clouds_global')
+        idxn, idxe, degs, degs_gpu, edgefeats = gc_info.get_buffers()
+        if idxe is not None:
+            raise NotImplementedError('filter sharing (idxe) is not supported by the fused RNN-ECC path')
+        s.graph = graph = gc_info.device_graph()
+        s.E = E = int(graph.E)
+        if graph.N != N:
+            raise ValueError(f'the batched graph has {graph.N} nodes, clouds_flag has {N} rows')
+        s.edgefeats = edgefeats = _req(edgefeats.contiguous().float(), torch.float32, 'edgefeats')
+        if training and plan['ecc_cfg'].bnidx >= 0 and E == 1:
+            raise ValueError('Expected more than 1 value per channel when training (filter-network BatchNorm over one edge)')
+        s.ecc_cfg = conv._cfg_for(plan['ecc_cfg'], gc_info, N)      # (+ the batch's scene boundaries for graphs above one round)
+        s.bufs = b = buffers(s, ctypes.byref(plan['ptn_cfg']), ctypes.byref(s.ecc_cfg))
+        s.logits = torch.empty(N, fc.out_features, dtype=torch.float32, device=s.dev)
+        a = _lib.StepArgs()
+        a.ptn_cfg, a.B = ctypes.pointer(plan['ptn_cfg']), B
+        a.clouds, a.clouds_global = clouds.data_ptr(), clouds_global.data_ptr()
+        a.ptn_params, a.ptn_ws, a.emb = plan['ptn_params'], b['ptn_ws'].data_ptr(), b['emb'].data_ptr()
+        a.N, a.nf = N, plan['nf']
+        a.slot_of_row, a.idx_valid, a.desc = s.slot_of_row.data_ptr(), s.idx_valid.data_ptr(), b['desc'].data_ptr()
+        a.ecc_cfg, a.E, a.graph_ws = ctypes.pointer(s.ecc_cfg), E, graph.ws.data_ptr()
+        a.edgefeats = edgefeats.data_ptr() if E else None
+        a.ecc_params, a.ecc_ws, a.ecc_out = plan['ecc_params'], b['ecc_ws'].data_ptr(), b['ecc_out'].data_ptr()
+        a.nout, a.n_classes = plan['nout'], fc.out_features
+        a.cls_W, a.cls_b, a.logits = fc.weight.data_ptr(), None if fc.bias is None else fc.bias.data_ptr(), s.logits.data_ptr()
+        return a, s
 
     def __call__(self, clouds_flag, clouds, clouds_global, gc_info, target):
         """-> (loss [] float32, logits [N, n_classes]) on the device, detached; gradients in the arena.
         clouds_flag / clouds / clouds_global: as CloudEmbedder.run takes them; gc_info: the batch's GraphConvInfo (already on
         the device: GraphNetwork.set_info(..., cuda=True) or set_batch_device); target: int64 [N] device tensor."""
-        from .learning.pointnet import stage_flags
-        model, ptn, conv, fc = self.model, self.ptn, self.conv, self.fc
+        ptn, conv, fc = self.ptn, self.conv, self.fc
         if not (ptn.training and conv.training):
             raise RuntimeError('FusedStep is a TRAINING step (model.train()); evaluate through the modules')
-        dev = torch.device('cuda', torch.cuda.current_device())
-        idx_valid, slot_of_row = stage_flags(clouds_flag)
-        clouds = ops.upload(clouds, dev) if not clouds.is_cuda else clouds
-        clouds_global = ops.upload(clouds_global, dev) if not clouds_global.is_cuda else clouds_global
-        clouds = _req(clouds.contiguous(), torch.float32, 'clouds')
-        B, N = int(clouds.shape[0]), int(clouds_flag.shape[0])
-        if B <= 1:
-            raise ValueError(f'Expected more than 1 value per channel when training, got input size [{B}, C]')
-        plan = self._tables(int(clouds.shape[2]))
-        if clouds.shape[1] != plan['ptn_cfg'].nfeat:
-            raise ValueError('clouds: wrong number of point features')
-        clouds_global = _req(clouds_global.reshape(B, -1).contiguous(), torch.float32, 'clouds_global')
-        idxn, idxe, degs, degs_gpu, edgefeats = gc_info.get_buffers()
-        if idxe is not None:
-            raise NotImplementedError('filter sharing (idxe) is not supported by the fused RNN-ECC path')
-        graph = gc_info.device_graph()
-        E = int(graph.E)
-        if graph.N != N:
-            raise ValueError(f'the batched graph has {graph.N} nodes, clouds_flag has {N} rows')
-        edgefeats = _req(edgefeats.contiguous().float(), torch.float32, 'edgefeats')
-        if plan['ecc_cfg'].bnidx >= 0 and E == 1:
-            raise ValueError('Expected more than 1 value per channel when training (filter-network BatchNorm over one edge)')
+
+        def buffers(s, pc, ec):
+            # (npts: the PointNet plan -- hence the workspace layout and the statistics slots -- depends on the points per cloud)
+            B, N, E, ecc_cfg = s.B, s.N, s.E, s.ecc_cfg
+            key = (B, N, E, s.dev, s.plan['npts'], tuple(ecc_cfg.part_ptr[:ecc_cfg.n_parts + 1]) if ecc_cfg.n_parts > 0 else ())
+
+            def make():
+                L, nf, nout, C = _lib.lib(), s.plan['nf'], s.plan['nout'], fc.out_features
+                ws = _workspaces(s.dev, L.spg_pointnet_workspace_bytes(pc, B, 1), L.spg_pointnet_bwd_workspace_bytes(pc, B),
+                                 L.spg_eccrnn_workspace_bytes(ec, N, E, 1), L.spg_eccrnn_bwd_workspace_bytes(ec, N, E))
+                f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=s.dev)
+                return dict(ptn_ws=ws[0], ptn_bwd_ws=ws[1], ecc_ws=ws[2], ecc_bwd_ws=ws[3], emb=f32(B, nf), grad_emb=f32(B, nf),
+                            desc=f32(N, nf), grad_desc=f32(N, nf), ecc_out=f32(N, nout), grad_ecc_out=f32(N, nout),
+                            cls_work=f32(max(1, L.spg_linear_wgrad_bias_work_floats(N, C, nout))), grad_logits=f32(N, C))
+            return self._buffers(key, make)
+        a, s = self._stage(True, clouds_flag, clouds, clouds_global, gc_info, buffers)
+        b, N = s.bufs, s.N
         target = _req(target.contiguous(), torch.int64, 'target')
-        ecc_cfg, _ = conv._cfg_for(gc_info, N)              # (+ the batch's scene boundaries for graphs above one round)
-        b = self._buffers(plan, B, N, E, dev, ecc_cfg)
-        C = fc.out_features
-        logits = torch.empty(N, C, dtype=torch.float32, device=dev)
-        loss_buf = torch.empty(N + 2, dtype=torch.float32, device=dev)
-        a = _lib.StepArgs()
-        a.ptn_cfg, a.B, a.bn_update_times = ctypes.pointer(plan['ptn_cfg']), B, self.bn_times
-        a.clouds, a.clouds_global = clouds.data_ptr(), clouds_global.data_ptr()
-        a.ptn_params, a.ptn_grads = plan['ptn_params'], plan['ptn_grads']
-        a.ptn_ws, a.ptn_bwd_ws, a.emb, a.grad_emb = b['ptn_ws'].data_ptr(), b['ptn_bwd_ws'].data_ptr(), b['emb'].data_ptr(), b['grad_emb'].data_ptr()
-        a.N, a.nf = N, plan['nf']
-        a.slot_of_row, a.idx_valid = slot_of_row.data_ptr(), idx_valid.data_ptr()
-        a.desc, a.grad_desc = b['desc'].data_ptr(), b['grad_desc'].data_ptr()
-        a.ecc_cfg, a.E, a.graph_ws = ctypes.pointer(ecc_cfg), E, graph.ws.data_ptr()
-        a.edgefeats = edgefeats.data_ptr() if E else None
-        a.ecc_params, a.ecc_grads = plan['ecc_params'], plan['ecc_grads']
-        a.ecc_ws, a.ecc_bwd_ws = b['ecc_ws'].data_ptr(), b['ecc_bwd_ws'].data_ptr()
-        a.ecc_out, a.grad_ecc_out = b['ecc_out'].data_ptr(), b['grad_ecc_out'].data_ptr()
-        a.nout, a.n_classes = plan['nout'], C
-        a.cls_W, a.cls_b = fc.weight.data_ptr(), None if fc.bias is None else fc.bias.data_ptr()
+        loss_buf = torch.empty(N + 2, dtype=torch.float32, device=s.dev)
+        a.bn_update_times = self.bn_times
+        a.ptn_grads, a.ptn_bwd_ws, a.grad_emb = s.plan['ptn_grads'], b['ptn_bwd_ws'].data_ptr(), b['grad_emb'].data_ptr()
+        a.grad_desc = b['grad_desc'].data_ptr()
+        a.ecc_grads, a.ecc_bwd_ws, a.grad_ecc_out = s.plan['ecc_grads'], b['ecc_bwd_ws'].data_ptr(), b['grad_ecc_out'].data_ptr()
         if fc.weight.grad is None or not fc.weight.grad.is_contiguous() or (fc.bias is not None and fc.bias.grad is None):
             raise RuntimeError('FusedStep: the classifier has no contiguous .grad view into the gradient arena')
         a.cls_dW, a.cls_db = fc.weight.grad.data_ptr(), None if fc.bias is None else fc.bias.grad.data_ptr()
-        a.cls_work, a.logits, a.grad_logits = b['cls_work'].data_ptr(), logits.data_ptr(), b['grad_logits'].data_ptr()
+        a.cls_work, a.grad_logits = b['cls_work'].data_ptr(), b['grad_logits'].data_ptr()
         a.target = target.data_ptr()
         a.class_weight = None if self.class_weights is None else self.class_weights.data_ptr()
         a.ignore_index, a.reduction_mean, a.loss_buf = self.ignore_index, int(self.mean), loss_buf.data_ptr()
@@ -192,75 +191,35 @@ class FusedStep:
         b['slots_clean'] = True
         # module-level bookkeeping the C call does not do -- only once the call has succeeded (a refused step must not advance
         # the BatchNorm batch counters or mark gradients as written)
-        ptn._bump_batches_tracked(self.bn_times)
-        for m in conv._fnet:
-            if isinstance(m, nn.BatchNorm1d) and m.num_batches_tracked is not None:
-                m.num_batches_tracked += 1
+        advance_batch_counters(ptn, self.bn_times)
+        advance_batch_counters(conv._fnet)
         for m in (ptn, conv, fc):
             mark_direct_write(m)
-        self._last = (plan['ptn_cfg'], B, b['ptn_ws'], ecc_cfg, graph, b['ecc_ws'], edgefeats)
+        self._last = (s.plan['ptn_cfg'], s.B, b['ptn_ws'], s.ecc_cfg, s.graph, b['ecc_ws'], s.edgefeats)
         self.normaliser = loss_buf[N + 1:N + 2]       # sum of the labelled rows' class weights (data-parallel loss weight w_r)
-        self._emb, self._slot = b['emb'], slot_of_row   # (the descriptors are read in place by the recurrence: see `embeddings`)
-        return loss_buf[N], logits
+        self._emb, self._slot = b['emb'], s.slot_of_row   # (the descriptors are read in place by the recurrence: see `embeddings`)
+        return loss_buf[N], s.logits
 
     def infer(self, clouds_flag, clouds, clouds_global, gc_info):
         """-> logits [N, n_classes] of the model in EVALUATION mode (model.eval(): BatchNorm running statistics), the body of
         the evaluation loop (learning/main.py:256-262) as ONE library call (spg_infer_step); same kernels and results as
         `model.ecc(CloudEmbedder.run(...))` under torch.no_grad()."""
-        from .learning.pointnet import stage_flags
-        ptn, conv, fc = self.ptn, self.conv, self.fc
-        if ptn.training or conv.training:
+        if self.ptn.training or self.conv.training:
             raise RuntimeError('FusedStep.infer is the EVALUATION forward (model.eval()); train with __call__')
-        dev = torch.device('cuda', torch.cuda.current_device())
-        idx_valid, slot_of_row = stage_flags(clouds_flag)
-        clouds = ops.upload(clouds, dev) if not clouds.is_cuda else clouds
-        clouds_global = ops.upload(clouds_global, dev) if not clouds_global.is_cuda else clouds_global
-        clouds = _req(clouds.contiguous(), torch.float32, 'clouds')
-        B, N = int(clouds.shape[0]), int(clouds_flag.shape[0])
-        if B < 1:
-            raise ValueError('no embeddable superpoint in the batch')
-        plan = self._tables(int(clouds.shape[2]))
-        if clouds.shape[1] != plan['ptn_cfg'].nfeat:
-            raise ValueError('clouds: wrong number of point features')
-        clouds_global = _req(clouds_global.reshape(B, -1).contiguous(), torch.float32, 'clouds_global')
-        idxn, idxe, degs, degs_gpu, edgefeats = gc_info.get_buffers()
-        if idxe is not None:
-            raise NotImplementedError('filter sharing (idxe) is not supported by the fused RNN-ECC path')
-        graph = gc_info.device_graph()
-        E = int(graph.E)
-        if graph.N != N:
-            raise ValueError(f'the batched graph has {graph.N} nodes, clouds_flag has {N} rows')
-        edgefeats = _req(edgefeats.contiguous().float(), torch.float32, 'edgefeats')
-        ecc_cfg, _ = conv._cfg_for(gc_info, N)
-        key = ('infer', B, N, E, dev)
-        b = self._bufs.get(key)
-        if b is None:
-            L = _lib.lib()
-            pc, ec = ctypes.byref(plan['ptn_cfg']), ctypes.byref(ecc_cfg)
-            sizes = (L.spg_pointnet_workspace_bytes(pc, B, 0), L.spg_eccrnn_workspace_bytes(ec, N, E, 0))
-            if min(sizes) == 0:
-                raise RuntimeError('workspace query failed: ' + L.spg_last_error().decode())
-            u8 = lambda n: torch.empty(max(int(n), 256), dtype=torch.uint8, device=dev)
-            f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
-            b = dict(ptn_ws=u8(sizes[0]), ecc_ws=u8(sizes[1]), emb=f32(B, plan['nf']), desc=f32(N, plan['nf']), ecc_out=f32(N, plan['nout']))
-            if len(self._bufs) >= 4:
-                self._bufs.pop(next(iter(self._bufs)))
-            self._bufs[key] = b
-        C = fc.out_features
-        logits = torch.empty(N, C, dtype=torch.float32, device=dev)
-        a = _lib.StepArgs()
-        a.ptn_cfg, a.B, a.bn_update_times = ctypes.pointer(plan['ptn_cfg']), B, 1
-        a.clouds, a.clouds_global = clouds.data_ptr(), clouds_global.data_ptr()
-        a.ptn_params, a.ptn_ws, a.emb = plan['ptn_params'], b['ptn_ws'].data_ptr(), b['emb'].data_ptr()
-        a.N, a.nf = N, plan['nf']
-        a.slot_of_row, a.idx_valid, a.desc = slot_of_row.data_ptr(), idx_valid.data_ptr(), b['desc'].data_ptr()
-        a.ecc_cfg, a.E, a.graph_ws = ctypes.pointer(ecc_cfg), E, graph.ws.data_ptr()
-        a.edgefeats = edgefeats.data_ptr() if E else None
-        a.ecc_params, a.ecc_ws, a.ecc_out = plan['ecc_params'], b['ecc_ws'].data_ptr(), b['ecc_out'].data_ptr()
-        a.nout, a.n_classes = plan['nout'], C
-        a.cls_W, a.cls_b, a.logits = fc.weight.data_ptr(), None if fc.bias is None else fc.bias.data_ptr(), logits.data_ptr()
+
+        def buffers(s, pc, ec):
+            B, N, E = s.B, s.N, s.E
+
+            def make():
+                L, nf = _lib.lib(), s.plan['nf']
+                ws = _workspaces(s.dev, L.spg_pointnet_workspace_bytes(pc, B, 0), L.spg_eccrnn_workspace_bytes(ec, N, E, 0))
+                f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=s.dev)
+                return dict(ptn_ws=ws[0], ecc_ws=ws[1], emb=f32(B, nf), desc=f32(N, nf), ecc_out=f32(N, s.plan['nout']))
+            return self._buffers(('infer', B, N, E, s.dev), make)
+        a, s = self._stage(False, clouds_flag, clouds, clouds_global, gc_info, buffers)
+        a.bn_update_times = 1
         _lib.check(_lib.lib().spg_infer_step(ctypes.byref(a), _stream()), 'spg_infer_step')
-        return logits
+        return s.logits
 
     def debug_states(self):
         """(PointNetState, EccRnnState) views of the LAST training step's forward workspaces -- what ops.pointnet_forward /

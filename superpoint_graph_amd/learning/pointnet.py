@@ -9,22 +9,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-
-
-def _seq_groups(seq):
-    """(weight, bias, norm.weight, norm.bias, running_mean, running_var) per parametric layer of a
-    Sequential[Conv1d|Linear, (BatchNorm1d|GroupNorm), ReLU, ...]."""
-    groups, mods = [], list(seq)
-    i = 0
-    while i < len(mods):
-        m = mods[i]
-        if isinstance(m, (nn.Conv1d, nn.Linear)):
-            bn = mods[i + 1] if i + 1 < len(mods) and isinstance(mods[i + 1], (nn.BatchNorm1d, nn.GroupNorm)) else None
-            groups.append((m, bn))
-        elif not isinstance(m, (nn.BatchNorm1d, nn.GroupNorm, nn.ReLU, nn.Dropout)):
-            raise NotImplementedError(f'{type(m).__name__} is not supported by the HIP PointNet (norm must be "batch", "layer" or "group")')
-        i += 1
-    return groups
+from . import _layers
 
 
 def _norm_module(norm, n_group, width):
@@ -36,6 +21,24 @@ def _norm_module(norm, n_group, width):
     if norm == 'group':
         return nn.GroupNorm(n_group, width)
     raise ValueError(f'norm must be "batch", "layer" or "group", got {norm!r}')
+
+
+def _stack(layer, nin, widths, norm, n_group, bare_last=False, prelast_do=0):
+    """The modules of a Sequential[layer(in, out), norm, ReLU, ...] over `widths`, constructed in the reference's order
+    (learning/pointnet.py:24-47, 81-105).  bare_last: neither norm nor ReLU behind the last layer; prelast_do: Dropout in front of it."""
+    modules = []
+    for i, width in enumerate(widths):
+        modules.append(layer(widths[i - 1] if i > 0 else nin, width))
+        if i < len(widths) - 1 or not bare_last:
+            modules.append(_norm_module(norm, n_group, width))
+            modules.append(nn.ReLU(True))
+        if i == len(widths) - 2 and prelast_do > 0:
+            modules.append(nn.Dropout(prelast_do))
+    return modules
+
+
+def _conv1x1(nin, nout):
+    return nn.Conv1d(nin, nout, 1)
 
 
 def _groupnorm_spec(*modules):
@@ -56,66 +59,44 @@ def _groupnorm_spec(*modules):
     return spec.pop()
 
 
-def _bn_momentum(bn):
-    """BatchNorm1d(momentum=None) means a cumulative moving average and track_running_stats=False means batch statistics
-    in eval mode: neither is implemented by the kernels (exponential average only) -- refuse instead of silently using 0.1."""
-    if bn.momentum is None:
-        raise NotImplementedError('BatchNorm1d(momentum=None) (cumulative average) is not implemented on the HIP path')
-    if not bn.track_running_stats or bn.running_mean is None:
-        raise NotImplementedError('BatchNorm1d(track_running_stats=False) is not implemented on the HIP path')
-    return bn.momentum
+class _LayerTable(nn.Module):
+    """What STNkD and PointNet share: `layer_groups()` -- their (Conv1d | Linear, norm-or-None) pairs -- as the rows of tensors
+    that the library takes."""
+    _spg_kernel_grads = True      # FlatParameters: the HIP backward writes the gradient views of every parameter below
+
+    def _groups_tensors(self):
+        return [_layers.layer_row(lin, norm) for lin, norm in self.layer_groups()]
+
+    def _bump_batches_tracked(self, times):
+        _layers.advance_batch_counters(self, times)
 
 
-def _tensors(lin, bn):
-    w = lin.weight
-    return (w, lin.bias, None if bn is None else bn.weight, None if bn is None else bn.bias,
-            getattr(bn, 'running_mean', None), getattr(bn, 'running_var', None))
-
-
-class STNkD(nn.Module):
+class STNkD(_LayerTable):
     """Spatial Transformer Net producing a KxK transformation matrix (reference learning/pointnet.py:16-61).
     Inside PointNet it is evaluated by the fused HIP pipeline; called on its own it runs the same kernels
     through a PointNet-less plan (K must be 2)."""
 
     def __init__(self, nfeat, nf_conv, nf_fc, K=2, norm='batch', affine=True, n_group=1):
         super(STNkD, self).__init__()
-        modules = []
-        for i in range(len(nf_conv)):
-            modules.append(nn.Conv1d(nf_conv[i - 1] if i > 0 else nfeat, nf_conv[i], 1))
-            modules.append(_norm_module(norm, n_group, nf_conv[i]))
-            modules.append(nn.ReLU(True))
-        self.convs = nn.Sequential(*modules)
-        modules = []
-        for i in range(len(nf_fc)):
-            modules.append(nn.Linear(nf_fc[i - 1] if i > 0 else nf_conv[-1], nf_fc[i]))
-            modules.append(_norm_module(norm, n_group, nf_fc[i]))
-            modules.append(nn.ReLU(True))
-        self.fcs = nn.Sequential(*modules)
+        self.convs = nn.Sequential(*_stack(_conv1x1, nfeat, nf_conv, norm, n_group))
+        self.fcs = nn.Sequential(*_stack(nn.Linear, nf_conv[-1], nf_fc, norm, n_group))
         self.proj = nn.Linear(nf_fc[-1], K * K)
         nn.init.constant_(self.proj.weight, 0)
         nn.init.constant_(self.proj.bias, 0)
         self.eye = torch.eye(K).unsqueeze(0)
         self._nfeat, self._nf_conv, self._nf_fc, self._K = nfeat, list(nf_conv), list(nf_fc), K
 
-    def layer_groups(self):
-        return _seq_groups(self.convs) + _seq_groups(self.fcs) + [(self.proj, None)]
-
     # ---- stand-alone evaluation (inside PointNet the STN is part of the fused pipeline) ----
     # An STN is structurally a PointNet segment without its own STN and without global features:
     # convs -> max-pool -> fcs -> plain last layer (proj); the same C entry points run it.
-    def _groups_tensors(self):
-        return [_tensors(lin, bn) for lin, bn in self.layer_groups()]
-
-    def _flat_params(self):
-        flat = []
-        for lin, bn in self.layer_groups():
-            flat += [lin.weight, lin.bias] + ([bn.weight, bn.bias] if bn is not None else [])
-        return [p for p in flat if p is not None]
+    def layer_groups(self):
+        return (_layers.layer_pairs(self.convs, _layers.POINTNET_STACK) + _layers.layer_pairs(self.fcs, _layers.POINTNET_STACK)
+                + [(self.proj, None)])
 
     def _cfg(self, npts):
         bn0 = self.convs[1]
         return ops.make_pointnet_cfg(self._nfeat, 0, 0, npts, [], [], self._nf_conv, self._nf_fc + [self._K * self._K], False,
-                                     bn0.eps, _bn_momentum(bn0))
+                                     bn0.eps, _layers.bn_momentum(bn0))
 
     def _gn_cfg(self, npts):
         n_group, eps = _groupnorm_spec(self)
@@ -126,79 +107,43 @@ class STNkD(nn.Module):
         if not input.is_cuda:
             raise RuntimeError('superpoint_graph_amd.STNkD has no CPU path; move the module and inputs to the GPU')
         self.eye = self.eye.to(input.device)
+        input, rows = input.contiguous().float(), self._groups_tensors()
         if _groupnorm_spec(self) is not None:      # norm = 'layer' | 'group': the cloud-resident kernels (spg_groupnorm.hip)
-            out = _GroupNormFunction.apply(self, input.contiguous().float(), None, None, *self._flat_params())
-            return out.view(-1, self.eye.size(1), self.eye.size(2)) + self.eye
-        if self.training:
-            nbt = [m.num_batches_tracked for m in self.modules() if isinstance(m, nn.BatchNorm1d)]
-            torch._foreach_add_(nbt, 1)
-        out = _PointNetFunction.apply(self, input.contiguous().float(), None, self.training, 1, *self._flat_params())
+            out = _GroupNormFunction.apply(self, rows, input, None, None, *_layers.flat_params(rows))
+        else:
+            if self.training:
+                self._bump_batches_tracked(1)
+            out = _PointNetFunction.apply(self, rows, input, None, None, self.training, 1, *_layers.node_inputs(self, rows, input.device))
         return out.view(-1, self.eye.size(1), self.eye.size(2)) + self.eye
 
 
-_anchors = {}
-
-
-def _grad_anchor(device):
-    """A 1-element tensor that requires grad: the single differentiable input of the HIP autograd nodes in
-    FlatParameters mode."""
-    a = _anchors.get(device)
-    if a is None:
-        a = torch.zeros(1, device=device, requires_grad=True)
-        _anchors[device] = a
-    return a
-
-
-def _direct_grad_targets(module, groups, nparam):
-    """When the module was wrapped by superpoint_graph_amd.flat.FlatParameters every parameter owns a .grad view
-    into one flat, pre-zeroed gradient buffer: return those views (structure of `groups`; `None` for the bias in
-    front of a BatchNorm, whose gradient is exactly zero) so that the kernels write into them directly."""
-    if not getattr(module, '_spg_direct_grads', False):
-        return None
-    out = []
-    for g in groups:
-        has_bn = nparam == 4 and g[2] is not None
-        row = []
-        for k in range(nparam):
-            t = g[k]
-            if t is None or (has_bn and k == 1):
-                row.append(None)
-                continue
-            if t.grad is None or not t.grad.is_contiguous():
-                return None
-            row.append(t.grad)
-        out.append(tuple(row))
-    return out
+def _minus_identity(T):
+    """[B, 4] = T - I of externally computed 2x2 matrices, as the *_ext entry points take them (None: no transform)."""
+    return None if T is None else T.reshape(-1, 4) - torch.eye(2, device=T.device, dtype=T.dtype).reshape(1, 4)
 
 
 class _PointNetFunction(torch.autograd.Function):
-    """autograd node around spg_pointnet_forward / spg_pointnet_backward; parameters are passed as inputs
-    so that autograd delivers their gradients."""
+    """autograd node around spg_pointnet_forward / spg_pointnet_backward; parameters are passed as inputs so that autograd
+    delivers their gradients (FlatParameters mode: one anchor, the kernels write into the arena).  With `T` it is a PointNet
+    WITHOUT inner STN whose xy channels are transformed by externally computed 2x2 matrices, differentiable wrt those
+    matrices and wrt the global features (what LocalCloudEmbedder.run_batch composes, learning/pointnet.py:188-205)."""
 
     @staticmethod
-    def forward(ctx, module, clouds, clouds_global, training, bn_update_times, *flat_params):
-        groups = module._groups_tensors()
-        emb, state = ops.pointnet_forward(module._cfg(clouds.shape[2]), clouds, clouds_global, groups, training, bn_update_times)
-        ctx.module, ctx.state, ctx.groups, ctx.nflat = module, state, groups, len(flat_params)
+    def forward(ctx, module, rows, clouds, clouds_global, T, training, bn_update_times, *flat_params):
+        emb, state = ops.pointnet_forward(module._cfg(clouds.shape[2]), clouds, clouds_global, rows, training, bn_update_times,
+                                          ext_transform=_minus_identity(T))
+        ctx.module, ctx.state, ctx.rows, ctx.nflat = module, state, rows, len(flat_params)
         return emb
 
     @staticmethod
     def backward(ctx, grad_emb):
-        direct = _direct_grad_targets(ctx.module, ctx.groups, 4)
-        if direct is not None:      # gradients are written straight into the pre-assigned .grad views (FlatParameters)
-            from ..flat import mark_direct_write
-            mark_direct_write(ctx.module)
-            ops.pointnet_backward(ctx.state, ctx.groups, grad_emb, direct)
-            return (None,) * (5 + ctx.nflat)
-        if ctx.nflat == 1 and getattr(ctx.module, '_spg_direct_grads', False):
-            raise RuntimeError('FlatParameters mode: a parameter has no contiguous .grad view into the gradient arena '
-                               '(optimizer.zero_grad(set_to_none=True) or a frozen parameter?); use FlatParameters.zero_grad()')
-        gg = ops.pointnet_backward(ctx.state, ctx.groups, grad_emb)
-        flat = []
-        for (gw, gb, ggam, gbet) in gg:
-            flat += [gw, gb, ggam, gbet]
-        flat = [g for g in flat if g is not None]
-        return (None, None, None, None, None) + tuple(flat)
+        def run(out_grads):
+            if ctx.state.ext_transform is None:
+                return ops.pointnet_backward(ctx.state, ctx.rows, grad_emb, out_grads), (None, None)
+            gg, g_T, g_glob = ops.pointnet_backward(ctx.state, ctx.rows, grad_emb, out_grads, want_input_grads=True)
+            return gg, (g_glob, g_T.view(-1, 2, 2))
+        flat, (g_glob, g_T) = _layers.arena_or_autograd(ctx.module, ctx.rows, ctx.nflat, run)
+        return (None, None, None, g_glob, g_T, None, None) + flat
 
 
 class _GroupNormFunction(torch.autograd.Function):
@@ -207,54 +152,23 @@ class _GroupNormFunction(torch.autograd.Function):
     2x2 matrices `T` (None: no transform) and the parameters.  Train and eval are the same function."""
 
     @staticmethod
-    def forward(ctx, module, clouds, clouds_global, T, *flat_params):
-        groups = module._groups_tensors()
-        ext = None
-        if T is not None:
-            ext = T.reshape(-1, 4) - torch.eye(2, device=T.device, dtype=T.dtype).reshape(1, 4)
-        out, state = ops.gn_forward(module._gn_cfg(clouds.shape[2]), clouds, clouds_global, groups, ext_transform=ext)
-        ctx.state, ctx.groups, ctx.glob_shape = state, groups, None if clouds_global is None else clouds_global.shape
+    def forward(ctx, module, rows, clouds, clouds_global, T, *flat_params):
+        out, state = ops.gn_forward(module._gn_cfg(clouds.shape[2]), clouds, clouds_global, rows, ext_transform=_minus_identity(T))
+        ctx.state, ctx.rows, ctx.glob_shape = state, rows, None if clouds_global is None else clouds_global.shape
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        gg, g_T, g_glob, g_clouds = ops.gn_backward(ctx.state, ctx.groups, grad_out, want_clouds=ctx.needs_input_grad[1])
+        gg, g_T, g_glob, g_clouds = ops.gn_backward(ctx.state, ctx.rows, grad_out, want_clouds=ctx.needs_input_grad[2])
         if g_T is not None:
             g_T = g_T.view(-1, 2, 2)
         if g_glob is not None:
             g_glob = g_glob.view(ctx.glob_shape)
         flat = [g for row in gg for g in row if g is not None]
-        return (None, g_clouds, g_glob, g_T) + tuple(flat)
+        return (None, None, g_clouds, g_glob, g_T) + tuple(flat)
 
 
-class _LocalPointNetFunction(torch.autograd.Function):
-    """PointNet WITHOUT inner STN whose xy channels are transformed by externally computed 2x2 matrices, differentiable
-    wrt those matrices and wrt the global features (what LocalCloudEmbedder.run_batch composes, learning/pointnet.py:188-205)."""
-
-    @staticmethod
-    def forward(ctx, module, clouds, clouds_global, T, training, *flat_params):
-        groups = module._groups_tensors()
-        eye = torch.eye(2, device=T.device, dtype=T.dtype).reshape(1, 4)
-        emb, state = ops.pointnet_forward(module._cfg(clouds.shape[2]), clouds, clouds_global, groups, training, 1,
-                                          ext_transform=T.reshape(-1, 4) - eye)
-        ctx.module, ctx.state, ctx.groups, ctx.nflat = module, state, groups, len(flat_params)
-        return emb
-
-    @staticmethod
-    def backward(ctx, grad_emb):
-        direct = _direct_grad_targets(ctx.module, ctx.groups, 4)
-        if direct is not None:
-            from ..flat import mark_direct_write
-            mark_direct_write(ctx.module)
-        gg, g_T, g_glob = ops.pointnet_backward(ctx.state, ctx.groups, grad_emb, direct, want_input_grads=True)
-        g_T = g_T.view(-1, 2, 2)
-        if direct is not None:
-            return (None, None, g_glob, g_T, None) + (None,) * ctx.nflat
-        flat = [g for row in gg for g in row if g is not None]
-        return (None, None, g_glob, g_T, None) + tuple(flat)
-
-
-class PointNet(nn.Module):
+class PointNet(_LayerTable):
     """PointNet with one spatial transformer and a "global" input concatenated after the max-pool
     (reference learning/pointnet.py:63-133; same constructor signature)."""
 
@@ -265,20 +179,8 @@ class PointNet(nn.Module):
         if nfeat_stn > 0:
             self.stn = STNkD(nfeat_stn, nf_conv_stn, nf_fc_stn, norm=norm, n_group=n_group)
         self.nfeat_stn = nfeat_stn
-        modules = []
-        for i in range(len(nf_conv)):
-            modules.append(nn.Conv1d(nf_conv[i - 1] if i > 0 else nfeat, nf_conv[i], 1))
-            modules.append(_norm_module(norm, n_group, nf_conv[i]))
-            modules.append(nn.ReLU(True))
-        self.convs = nn.Sequential(*modules)
-        modules = []
-        for i in range(len(nf_fc)):
-            modules.append(nn.Linear(nf_fc[i - 1] if i > 0 else nf_conv[-1] + nfeat_global, nf_fc[i]))
-            if i < len(nf_fc) - 1 or last_ac:
-                modules.append(_norm_module(norm, n_group, nf_fc[i]))
-                modules.append(nn.ReLU(True))
-            if i == len(nf_fc) - 2 and prelast_do > 0:
-                modules.append(nn.Dropout(prelast_do))
+        self.convs = nn.Sequential(*_stack(_conv1x1, nfeat, nf_conv, norm, n_group))
+        modules = _stack(nn.Linear, nf_conv[-1] + nfeat_global, nf_fc, norm, n_group, not last_ac, prelast_do)
         if is_res:
             nn.init.normal_(modules[-1].weight, mean=0, std=1e-2)
             nn.init.normal_(modules[-1].bias, mean=0, std=1e-2)
@@ -290,19 +192,10 @@ class PointNet(nn.Module):
     def layer_groups(self):
         lg = self.__dict__.get('_lg_cache')
         if lg is None:                # the module structure is fixed after construction
-            g = self.stn.layer_groups() if self.nfeat_stn > 0 else []
-            lg = g + _seq_groups(self.convs) + _seq_groups(self.fcs)
+            lg = self.stn.layer_groups() if self.nfeat_stn > 0 else []
+            lg = lg + _layers.layer_pairs(self.convs, _layers.POINTNET_STACK) + _layers.layer_pairs(self.fcs, _layers.POINTNET_STACK)
             self.__dict__['_lg_cache'] = lg
         return lg
-
-    def _groups_tensors(self):
-        return [_tensors(lin, bn) for lin, bn in self.layer_groups()]
-
-    def _flat_params(self):
-        flat = []
-        for lin, bn in self.layer_groups():
-            flat += [lin.weight, lin.bias] + ([bn.weight, bn.bias] if bn is not None else [])
-        return [p for p in flat if p is not None]
 
     def _cfg(self, npts):
         cache = self.__dict__.setdefault('_cfg_cache', {})
@@ -311,7 +204,7 @@ class PointNet(nn.Module):
             stn_fc = self.stn._nf_fc if self.nfeat_stn > 0 else []
             bn0 = self.convs[1]
             cache[npts] = ops.make_pointnet_cfg(self._nfeat, self.nfeat_stn, self._nfeat_global, npts, stn_conv, stn_fc,
-                                                self._nf_conv, self._nf_fc, self._last_ac, bn0.eps, _bn_momentum(bn0))
+                                                self._nf_conv, self._nf_fc, self._last_ac, bn0.eps, _layers.bn_momentum(bn0))
         return cache[npts]
 
     def _gn_spec(self):
@@ -330,14 +223,6 @@ class PointNet(nn.Module):
         n_group, eps = self._gn_spec()
         return ops.make_gn_cfg(self._nfeat, self._nfeat_global, npts, self._nf_conv, self._nf_fc, n_group, eps, self._last_ac)
 
-    def _bump_batches_tracked(self, times):
-        nbt = self.__dict__.get('_nbt_cache')
-        if nbt is None:
-            nbt = [m for m in self.modules() if isinstance(m, nn.BatchNorm1d) and m.num_batches_tracked is not None]
-            self.__dict__['_nbt_cache'] = nbt
-        if nbt:
-            torch._foreach_add_([m.num_batches_tracked for m in nbt], times)   # one launch for all BatchNorm layers
-
     def forward(self, input, input_global, bn_update_times=1):
         if not input.is_cuda:
             raise RuntimeError('superpoint_graph_amd.PointNet has no CPU path; move the model and inputs to the GPU')
@@ -345,16 +230,13 @@ class PointNet(nn.Module):
             raise NotImplementedError('ptn_prelast_do > 0 (dropout before the last layer) is not implemented on the HIP path')
         if self.nfeat_stn > 0 and self.stn._K != 2:
             raise NotImplementedError('the fused STN applies a 2x2 transform (K=2), as PointNet.forward does')
-        input = input.contiguous().float()
+        input, rows = input.contiguous().float(), self._groups_tensors()
         if self._gn_spec() is not None:      # norm = 'layer' | 'group': the cloud-resident kernels (spg_groupnorm.hip)
-            return _GroupNormFunction.apply(self, input, input_global, None, *self._flat_params())
+            return _GroupNormFunction.apply(self, rows, input, input_global, None, *_layers.flat_params(rows))
         if self.training:
             self._bump_batches_tracked(bn_update_times)
-        if getattr(self, '_spg_direct_grads', False) and torch.is_grad_enabled():
-            # FlatParameters mode: gradients are written into the arena by the kernels, so autograd only needs ONE
-            # differentiable input to create the node (instead of tracking ~60 parameter tensors)
-            return _PointNetFunction.apply(self, input, input_global, self.training, bn_update_times, _grad_anchor(input.device))
-        return _PointNetFunction.apply(self, input, input_global, self.training, bn_update_times, *self._flat_params())
+        return _PointNetFunction.apply(self, rows, input, input_global, None, self.training, bn_update_times,
+                                       *_layers.node_inputs(self, rows, input.device))
 
 
 class LocalCloudEmbedder():
@@ -403,8 +285,9 @@ class LocalCloudEmbedder():
                 clouds_global = torch.cat([clouds_global, T.reshape(-1, 4)], 1)
             if ptn.training:
                 ptn._bump_batches_tracked(1)
-            extra = (_grad_anchor(clouds.device),) if getattr(ptn, '_spg_direct_grads', False) and torch.is_grad_enabled() else tuple(ptn._flat_params())
-            out = _LocalPointNetFunction.apply(ptn, clouds, clouds_global.contiguous(), T, ptn.training, *extra)
+            rows = ptn._groups_tensors()
+            out = _PointNetFunction.apply(ptn, rows, clouds, clouds_global.contiguous(), T, ptn.training, 1,
+                                          *_layers.node_inputs(ptn, rows, clouds.device))
         else:
             out = ptn(clouds, clouds_global.contiguous())
         return nn.functional.normalize(out)
@@ -425,7 +308,8 @@ class LocalCloudEmbedder():
             T = model.stn(clouds[:, :2, :].contiguous())
             if self.stn_as_global:
                 clouds_global = torch.cat([clouds_global, T.reshape(-1, 4)], 1)
-        out = _GroupNormFunction.apply(ptn, clouds, clouds_global.contiguous(), T, *ptn._flat_params())
+        rows = ptn._groups_tensors()
+        out = _GroupNormFunction.apply(ptn, rows, clouds, clouds_global.contiguous(), T, *_layers.flat_params(rows))
         return nn.functional.normalize(out)
 
     def run_batch_cpu(self, model, clouds, clouds_global, *excess):

@@ -228,6 +228,21 @@ def _require_training_state(state, what):
                            'or wrap the eval-mode forward in torch.no_grad()')
 
 
+def rows6(rows):
+    """Every row padded with None to the six pointers per layer of the library's tables."""
+    return [tuple(r) + (None,) * (6 - len(r)) for r in rows]
+
+
+def _grad_rows(groups, live, out_grads=None):
+    """Six gradient destinations per row of `groups`: the first `live[li]` are `out_grads[li]`'s (written, not accumulated; a
+    None entry is skipped by the library) or fresh tensors shaped like the parameters; the running statistics have none."""
+    if out_grads is not None:
+        if len(out_grads) != len(groups):
+            raise ValueError(f'out_grads: {len(groups)} rows expected, got {len(out_grads)}')
+        return rows6(tuple(d[:n]) for d, n in zip(out_grads, live))
+    return rows6(tuple(None if t is None else torch.empty_like(t) for t in g[:n]) for g, n in zip(groups, live))
+
+
 class PointNetState:
     """Saved forward state (workspace with the raw layer outputs and BatchNorm constants)."""
 
@@ -286,14 +301,8 @@ def pointnet_backward(state: PointNetState, groups, grad_emb, out_grads=None, wa
     grad_emb = _req(grad_emb.contiguous(), torch.float32, 'grad_emb')
     nbytes = lib().spg_pointnet_bwd_workspace_bytes(ctypes.byref(cfg), B)
     bws = torch.empty(nbytes, dtype=torch.uint8, device=grad_emb.device)
-    gg, flatg = [], []
-    for li, g in enumerate(groups):
-        if out_grads is not None:
-            d = list(out_grads[li][:4])
-        else:
-            d = [None if g[k] is None else torch.empty_like(g[k]) for k in range(4)]
-        gg.append(tuple(d))
-        flatg += d + [None, None]
+    grows = _grad_rows(groups, [4] * len(groups), out_grads)
+    gg, flatg = [r[:4] for r in grows], [t for r in grows for t in r]
     flat = [t for g in groups for t in g]
     g_T = g_glob = None
     if want_input_grads:          # gradients wrt the external transform and the global features (LocalCloudEmbedder)
@@ -373,7 +382,8 @@ def gn_backward(state: GroupNormState, groups, grad_emb, want_clouds=False):
     cfg, B = state.cfg, state.B
     grad_emb = _req(grad_emb.contiguous(), torch.float32, 'grad_emb')
     dev = grad_emb.device
-    gg = [tuple(None if g[k] is None else torch.empty_like(g[k]) for k in range(4)) for g in groups]
+    grows = _grad_rows(groups, [4] * len(groups))
+    gg = [r[:4] for r in grows]
     g_T = torch.empty(B, 4, dtype=torch.float32, device=dev) if state.ext_transform is not None else None
     g_glob = torch.empty_like(state.clouds_global) if state.clouds_global is not None else None
     g_clouds = torch.empty_like(state.clouds) if want_clouds else None
@@ -382,7 +392,7 @@ def gn_backward(state: GroupNormState, groups, grad_emb, want_clouds=False):
     nbytes = lib().spg_gn_bwd_workspace_bytes(ctypes.byref(cfg), B)
     bws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     flat = [t for g in groups for t in g]
-    flatg = [t for row in gg for t in list(row) + [None, None]]
+    flatg = [t for r in grows for t in r]
     _gn_check(lib().spg_gn_backward_ext(ctypes.byref(cfg), B, _ptr(state.clouds), _ptr(state.clouds_global), _ptr(state.ext_transform),
                                         _ptr_array(flat), _ptr(grad_emb), _ptr_array(flatg), _ptr(g_T), _ptr(g_glob), _ptr(g_clouds),
                                         _ptr(state.ws), _ptr(bws), _stream()), 'spg_gn_backward_ext')
@@ -441,17 +451,8 @@ def eccrnn_backward(state: EccRnnState, groups, grad_out, out_grads=None):
     grad_out = _req(grad_out.contiguous(), torch.float32, 'grad_out')
     bws = torch.empty(lib().spg_eccrnn_bwd_workspace_bytes(ctypes.byref(cfg), N, E), dtype=torch.uint8, device=grad_out.device)
     grad_h0 = torch.empty(N, cfg.nc, dtype=torch.float32, device=grad_out.device)
-    gg, flatg = [], []
-    nf = cfg.n_fnet
-    for li, g in enumerate(groups):
-        if out_grads is not None:
-            d = (list(out_grads[li][:4]) + [None, None]) if li < nf else list(out_grads[li][:6])
-        elif li < nf:
-            d = [None if g[k] is None else torch.empty_like(g[k]) for k in range(4)] + [None, None]
-        else:
-            d = [None if g[k] is None else torch.empty_like(g[k]) for k in range(6)]
-        gg.append(tuple(d))
-        flatg += d
+    gg = _grad_rows(groups, [4] * cfg.n_fnet + [6] * (len(groups) - cfg.n_fnet), out_grads)      # layers of the filter network, then the cell
+    flatg = [t for r in gg for t in r]
     flat = [t for g in groups for t in g]
     check(lib().spg_eccrnn_backward(ctypes.byref(cfg), N, E, _ptr(graph.ws), _ptr(state.edgefeats), _ptr_array(flat),
                                     _ptr(grad_out), _ptr(grad_h0), _ptr_array(flatg), _ptr(state.ws), _ptr(bws), _stream()),

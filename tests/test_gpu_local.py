@@ -103,6 +103,26 @@ def test_local_cloud_embedder_other_shapes_vs_oracle(hip, n, k):
     _grad_check({kk: p.grad for kk, p in model.named_parameters()}, {kk: gg.numpy() for kk, gg in zip(leaves, go)}, 5e-4)
 
 
+def test_local_cloud_embedder_missing_grad_view_is_refused_before_any_launch(hip):
+    """FlatParameters mode, 4 clouds of 16 points (the smallest shape the path takes): a `ptn` parameter without its .grad view
+    into the arena makes the backward raise the arena error before it launches anything -- no gradient of `ptn` is written, no
+    parameter changes -- instead of running the kernels and failing in autograd afterwards."""
+    from superpoint_graph_amd.flat import FlatParameters
+    from superpoint_graph_amd.learning import pointnet
+    model = _product_model().cuda().train()
+    arena = FlatParameters(model)
+    clouds, cg, w = V.local_inputs(4, 16)
+    arena.zero_grad()
+    emb = pointnet.LocalCloudEmbedder(ARGS).run_batch(model, clouds.cuda(), cg.cuda())
+    before = arena.flat.data.clone()
+    model.ptn.convs[3].weight.grad = None
+    with pytest.raises(RuntimeError, match='FlatParameters mode: a parameter has no contiguous .grad view into the gradient arena'):
+        (emb * w.cuda()).sum().backward()
+    assert torch.equal(arena.flat.data, before)
+    assert all(p.grad is None or not bool(p.grad.any()) for p in model.ptn.parameters())
+    assert not model.ptn._spg_grad_written
+
+
 def test_local_cloud_embedder_beyond_the_chunk_boundary(hip):
     """2^16 + 40 clouds: in training mode the reference evaluates 2^16 - 1 clouds and then 41 as SEPARATE BatchNorm batches
     (pointnet.py:193-206); rows on both sides of the boundary, column sums, four gradient tensors and the running
