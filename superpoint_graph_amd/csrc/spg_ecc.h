@@ -1,6 +1,7 @@
 // Internal (C++) interface of the edge-conditioned-convolution / GRU kernels (spg_ecc.hip).
 #pragma once
 #include "spg_common.h"
+#include "spg_px_plan.h"
 
 // Device-side graph structure derived from GraphConvInfo's (idxn, degs)
 // (reference: learning/ecc/GraphConvInfo.py:33-69): CSR by target (edges are already sorted by
@@ -137,18 +138,7 @@ int spg_launch_ecc_edge_wgrad(const SpgGraph& g, int matrix, const float* states
 int spg_launch_copy2d(const float* src, long lds, float* dst, long ldd, long rows, int cols, hipStream_t stream);
 
 // ---- persistent (one launch for all iterations) forms of the GRU recurrence, spg_ecc.hip ----
-#define SPG_PX_WG_NODES 1024       // nodes per round with ONE 4-wave workgroup per CU (one wavefront per node, all co-resident)
-#define SPG_PX_MAX_NODES 2048      // nodes per round with two workgroups per CU (fewer register-resident filters, gate rows from LDS)
-#define SPG_PX_MAX_GROUPS 8        // rounds per launch: groups of whole connected components (scenes) of <= SPG_PX_MAX_NODES nodes
-#define SPG_PX_MULTI_MAX_NODES 16000      // one group above SPG_PX_MAX_NODES: several nodes per wavefront, iteration-major (spg_ecc.hip)
-inline bool spg_px_is_multi(int n_groups, int max_group) { return n_groups == 1 && max_group > SPG_PX_MAX_NODES; }
-struct SpgPxGroups {               // node ranges [ptr[g], ptr[g+1]) of the rounds; n = 1: the whole graph in one round
-  int n;
-  int ptr[SPG_PX_MAX_GROUPS + 1];
-};
-// rounds for a batch whose connected components are unions of the node ranges part_ptr[0..n_parts] (scenes of a batch; n_parts
-// = 0: unknown -- one round if the whole graph fits); false when a part exceeds a round or too many rounds would be needed
-bool spg_px_plan_groups(int N, int n_parts, const int* part_ptr, SpgPxGroups* out);
+// (the limits, the rounds and the launch plan: spg_px_plan.h)
 #define SPG_PX_SAVE_F 12           // floats per lane and (node, iteration) of forward internals kept for the backward (3 quads)
 // What follows the recurrence in the standard model -- the classifier Linear(nin -> C) on the module's output (h^R, or all of
 // h^0 .. h^R with cat_all: nin = 32 or 32 (R + 1); learning/graphnet.py:47-49,81) and the weighted cross entropy of the trainer

@@ -946,7 +946,6 @@ int spg_launch_copy2d(const float* src, long lds, float* dst, long ldd, long row
 // time (launches of one stream serialise; a second stream falls back to the per-iteration kernels).  Spins are bounded: a
 // wave that waits longer than SPG_PX_SPIN_LIMIT sweeps raises the error word of the control block (spg_ecc_persistent_errors)
 // and carries on, so a logic error can never hang the GPU.
-#define SPG_PX_MAX_ITERS 16
 #define SPG_PX_KMAX1 12        // edges per node whose filters stay in registers (16 VGPRs each in matrix mode), one workgroup per CU
 #define SPG_PX_KMAX2 6         // ... with two workgroups per CU (256 VGPRs per wave), forward
 #define SPG_PX_KMAX2B 2        // ... backward
@@ -1753,7 +1752,6 @@ __global__ __launch_bounds__(256, WPC) void spg_ecc_persist_bwd_kernel(const Spg
 // (the "beyond KMAX" path of the kernels above: same arithmetic, same order), the nodes' states travel through LDS (forward: h,
 // backward: the direct gradient path), the cell's internals are recomputed by the backward (no fsave: 3 KB per node and iteration).
 // No head, no service workgroups, one group.  Granule region: [iteration][p.gran_nodes][32].
-#define SPG_PX_MULTI_NPW 8
 template <bool MATRIX>
 __global__ __launch_bounds__(256, 3) void spg_ecc_persist_fwd_multi_kernel(const SpgEccPersistFwd p) {
   __shared__ float sw[(2 * 96 + 32) * SPG_WLD];
@@ -1987,6 +1985,7 @@ __global__ __launch_bounds__(256, 2) void spg_ecc_persist_bwd_multi_kernel(const
 }
 
 // ---- host side: the exchange buffer and the launchers ----
+// (which form a launch takes and how many workgroups: spg_px_plan.h; here only what needs the runtime)
 static void* g_px_buf[SPG_MAX_DEVICES] = {nullptr};
 static hipStream_t g_px_stream[SPG_MAX_DEVICES] = {nullptr};
 static bool g_px_stream_set[SPG_MAX_DEVICES] = {false};
@@ -1996,57 +1995,20 @@ static size_t px_bytes() {
   return SPG_PX_CTL_BYTES + (size_t)SPG_PX_MAX_GROUPS * SPG_PX_MAX_ITERS * SPG_PX_MAX_NODES * 32 * sizeof(unsigned long long);
 }
 
-// Rounds of a launch: consecutive parts (connected components / scenes) are packed greedily into groups of at most `cap` nodes
-bool spg_px_plan_groups(int N, int n_parts, const int* part_ptr, SpgPxGroups* out) {
-  const int cap = SPG_PX_MAX_NODES;
-  out->n = 0;
-  if (N <= 0) return false;
-  if (N <= cap) { out->n = 1; out->ptr[0] = 0; out->ptr[1] = N; return true; }      // one round, whatever the components
-  // components unknown, or one of them above a round: ONE group with several nodes per wavefront (the iteration-major kernels)
-  auto big = [&]() -> bool {
-    if (N > SPG_PX_MULTI_MAX_NODES || spg_tune_get(SPG_TUNE_NO_PERSIST_ECC) == 2) return false;
-    out->n = 1; out->ptr[0] = 0; out->ptr[1] = N;
-    return true;
-  };
-  if (n_parts <= 0 || part_ptr == nullptr || part_ptr[0] != 0 || part_ptr[n_parts] != N) return big();
-  int start = 0;
-  out->ptr[0] = 0;
-  for (int k = 0; k < n_parts; ++k) {
-    const int a = part_ptr[k], b = part_ptr[k + 1];
-    if (b < a) return false;
-    if (b - a > cap) return big();
-    if (b - start > cap) {                // part k opens a new group
-      if (out->n + 1 >= SPG_PX_MAX_GROUPS) return big();
-      out->ptr[++out->n] = a;
-      start = a;
-    }
-  }
-  out->ptr[++out->n] = N;
-  return true;
+static int px_device() {      // the current device, or -1
+  int dev = 0;
+  return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < SPG_MAX_DEVICES ? dev : -1;
+}
+static int px_cus(int dev) {      // its CUs, asked once per device; 0: the query failed.  The caller holds g_px_mutex.
+  static int cus[SPG_MAX_DEVICES] = {0};
+  int n = 0;
+  if (cus[dev] == 0 && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) cus[dev] = n;
+  return cus[dev];
 }
 
-// largest round of a plan -> workgroups per CU the launch needs (1: <= SPG_PX_WG_NODES nodes per round)
-static int px_max_group(const SpgPxGroups& g) {
-  int m = 0;
-  for (int k = 0; k < g.n; ++k) m = g.ptr[k + 1] - g.ptr[k] > m ? g.ptr[k + 1] - g.ptr[k] : m;
-  return m;
-}
-
-// returns the exchange buffer of the current device, or null when the persistent form must not be used for this launch
-static char* px_acquire(const SpgPxGroups& groups, int R, hipStream_t stream) {
-  if (spg_tune_get(SPG_TUNE_NO_PERSIST_ECC) == 1 || groups.n < 1 || R + 1 > SPG_PX_MAX_ITERS || R < 1) return nullptr;      // (2: only the iteration-major form is off, spg_px_plan_groups)
-  const int mg = px_max_group(groups);
-  const bool multi = spg_px_is_multi(groups.n, mg);
-  if (mg > SPG_PX_MAX_NODES && !multi) return nullptr;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= SPG_MAX_DEVICES) return nullptr;
-  // every workgroup must be resident at once (one or two 4-wave workgroups per CU): a few CUs of margin
-  const int wpc = mg > SPG_PX_WG_NODES ? 2 : 1;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return nullptr;
-  if (multi) {      // several nodes per wavefront: the wavefronts of two workgroups per CU must cover the nodes, the granules fit the buffer
-    if (mg > 4 * 2 * (cus - 4) * SPG_PX_MULTI_NPW || (long)(R + 1) * mg > (long)SPG_PX_MAX_GROUPS * SPG_PX_MAX_ITERS * SPG_PX_MAX_NODES) return nullptr;
-  } else if (spg_cdiv(mg, 4) > wpc * (cus - 4)) return nullptr;
-  std::lock_guard<std::mutex> lock(g_px_mutex);
+// returns the exchange buffer of device `dev`, or null when the persistent form must not be used for this launch.  The caller
+// holds g_px_mutex.
+static char* px_acquire(int dev, hipStream_t stream) {
   if (g_px_buf[dev] == nullptr) {
     void* b = nullptr;
     if (hipMalloc(&b, px_bytes()) != hipSuccess) return nullptr;
@@ -2071,14 +2033,6 @@ static char* px_acquire(const SpgPxGroups& groups, int R, hipStream_t stream) {
   return (char*)g_px_buf[dev];
 }
 
-// workgroups the launch may add beyond its node workgroups without leaving the residency bound px_acquire checked
-static int px_spare_wgs(int node_wgs, int wpc) {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-  const int spare = wpc * (cus - 4) - node_wgs;
-  return spare > 0 ? spare : 0;
-}
-
 // Workgroups per CU the iteration-major kernels REALLY get (registers, LDS; a build for another gfx target or a device whose CUs
 // are partly masked gives fewer than the numbers they were written for): asked once per kernel.  A grid above what is resident
 // would leave waves spinning to their bound for workgroups that cannot start.
@@ -2088,7 +2042,7 @@ static int px_occupancy(K kernel, int want) {
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, 256, 0) != hipSuccess || n < 1) return 0;
   return n < want ? n : want;
 }
-static int px_multi_wpc(bool matrix, bool backward) {
+static int px_multi_wpc(bool matrix, bool backward) {      // (the forward needs 168 registers and 52 KB of LDS: three workgroups per CU on gfx950)
   static int cache[2][2] = {{-1, -1}, {-1, -1}};
   int& c = cache[matrix ? 1 : 0][backward ? 1 : 0];
   if (c < 0) {
@@ -2098,61 +2052,76 @@ static int px_multi_wpc(bool matrix, bool backward) {
   return c;
 }
 
-// workgroups of an iteration-major launch: as many as stay resident with `wpc` per CU, no more than one wavefront per node
-static int px_multi_wgs(int nodes, int wpc = 2) {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 64;
-  const int cap = wpc * (cus - 4), need = spg_cdiv(nodes, 4);
-  return need < cap ? need : cap;
+// The plan of launch `p` on the current device, then -- unless it declines -- the exchange buffer, and what both give of p.
+// false: the per-iteration launches.
+template <class P>
+static bool px_prepare(P& p, bool backward, const SpgPxHeadFacts& head, hipStream_t stream, SpgPxPlan* pl) {
+  std::lock_guard<std::mutex> lock(g_px_mutex);      // the one lock of a launch: CU count, buffer, stream hand-over
+  const int dev = px_device(), cus = dev < 0 ? 0 : px_cus(dev);
+  if (cus < 1) return false;
+  const int occupancy = spg_px_groups_multi(p.groups) ? px_multi_wpc(p.matrix != 0, backward) : 0;
+  *pl = spg_px_plan(p.groups, p.R, backward, cus, occupancy, spg_tune_get(SPG_TUNE_NO_PERSIST_ECC), head);
+  char* buf = pl->form == SPG_PX_DECLINED ? nullptr : px_acquire(dev, stream);
+  if (buf == nullptr) return false;
+  p.ctl = (unsigned*)buf;
+  p.gran = (unsigned long long*)(buf + SPG_PX_CTL_BYTES);
+  p.node_wgs = pl->node_wgs;
+  p.gran_nodes = pl->gran_nodes;
+  return true;
 }
 
-extern "C" int spg_ecc_persistent_errors(void) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= SPG_MAX_DEVICES || g_px_buf[dev] == nullptr) return 0;
-  unsigned ctl[4] = {0, 0, 0, 0};
-  if (hipMemcpy(ctl, g_px_buf[dev], sizeof(ctl), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-  return (int)ctl[2];
+// the exchange buffer of the current device; null while it has none, or without a valid current device (*no_device)
+static char* px_current_buf(bool* no_device = nullptr) {
+  const int dev = px_device();
+  if (no_device != nullptr) *no_device = dev < 0;
+  return dev < 0 ? nullptr : (char*)g_px_buf[dev];
 }
+// ctl[0..3] of that buffer (one blocking 16-byte copy); buf == nullptr: no buffer, nothing read
+struct PxCtl { char* buf; hipError_t err; unsigned w[4]; };
+static PxCtl px_read_ctl(bool* no_device = nullptr) {
+  PxCtl c = {px_current_buf(no_device), hipSuccess, {0, 0, 0, 0}};
+  if (c.buf != nullptr) c.err = hipMemcpy(c.w, c.buf, sizeof(c.w), hipMemcpyDeviceToHost);
+  return c;
+}
+// zeroes the error word and the withheld-update counter (ctl[2], ctl[3]) where one of them was read as set
+static hipError_t px_clear_ctl(const PxCtl& c) {
+  const unsigned zero[2] = {0u, 0u};
+  if (c.w[2] == 0u && c.w[3] == 0u) return hipSuccess;
+  return hipMemcpy(c.buf + 2 * sizeof(unsigned), zero, sizeof(zero), hipMemcpyHostToDevice);
+}
+
+// the error word; clear: reads AND clears it (call that where the host synchronises anyway)
+static int px_errors(bool clear) {
+  const PxCtl c = px_read_ctl();
+  if (c.buf == nullptr) return 0;
+  return c.err != hipSuccess || (clear && px_clear_ctl(c) != hipSuccess) ? -1 : (int)c.w[2];
+}
+extern "C" int spg_ecc_persistent_errors(void) { return px_errors(false); }
+extern "C" int spg_ecc_persistent_errors_clear(void) { return px_errors(true); }
 
 // The fail-safe of the optimiser step (spg_adam_clamp_kernel, spg_api.hip): device address of the control block's error word
 // (ctl[2]; ctl[3] counts the update launches that were withheld because of it), or null while the device has no exchange buffer
 // (no persistent launch has run: nothing can have timed out).
 unsigned* spg_px_guard_words() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= SPG_MAX_DEVICES || g_px_buf[dev] == nullptr) return nullptr;
-  return (unsigned*)g_px_buf[dev] + 2;
+  char* buf = px_current_buf();
+  return buf == nullptr ? nullptr : (unsigned*)buf + 2;
 }
 
 extern "C" int spg_ecc_persistent_status(int* errors, int* withheld, int clear) {
   if (errors) *errors = 0;
   if (withheld) *withheld = 0;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= SPG_MAX_DEVICES) { spg_set_error("spg_ecc_persistent_status: no current device"); return -1; }
-  if (g_px_buf[dev] == nullptr) return 0;
-  unsigned ctl[4] = {0, 0, 0, 0};
-  hipError_t e = hipMemcpy(ctl, g_px_buf[dev], sizeof(ctl), hipMemcpyDeviceToHost);
+  bool no_device = false;
+  const PxCtl c = px_read_ctl(&no_device);
+  if (no_device) { spg_set_error("spg_ecc_persistent_status: no current device"); return -1; }
+  if (c.buf == nullptr) return 0;
+  hipError_t e = c.err;
+  if (e == hipSuccess) {
+    if (errors) *errors = (int)c.w[2];
+    if (withheld) *withheld = (int)c.w[3];
+    if (clear) e = px_clear_ctl(c);
+  }
   if (e != hipSuccess) { spg_set_error("spg_ecc_persistent_status: %s", hipGetErrorString(e)); return (int)e; }
-  if (errors) *errors = (int)ctl[2];
-  if (withheld) *withheld = (int)ctl[3];
-  if (clear && (ctl[2] != 0u || ctl[3] != 0u)) {
-    const unsigned zero[2] = {0u, 0u};
-    e = hipMemcpy((char*)g_px_buf[dev] + 2 * sizeof(unsigned), zero, sizeof(zero), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { spg_set_error("spg_ecc_persistent_status: %s", hipGetErrorString(e)); return (int)e; }
-  }
   return 0;
-}
-
-// reads AND clears the error word (one blocking 16-byte copy each way: call it where the host synchronises anyway)
-extern "C" int spg_ecc_persistent_errors_clear(void) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= SPG_MAX_DEVICES || g_px_buf[dev] == nullptr) return 0;
-  unsigned ctl[4] = {0, 0, 0, 0};
-  if (hipMemcpy(ctl, g_px_buf[dev], sizeof(ctl), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-  if (ctl[2] != 0u || ctl[3] != 0u) {
-    const unsigned zero[2] = {0u, 0u};
-    if (hipMemcpy((char*)g_px_buf[dev] + 2 * sizeof(unsigned), zero, sizeof(zero), hipMemcpyHostToDevice) != hipSuccess) return -1;
-  }
-  return (int)ctl[2];
 }
 
 // KMAX of the variants: forward 12 / 6 register-resident filters (1 / 2 workgroups per CU); the backward's own working set is
@@ -2180,29 +2149,16 @@ bool spg_launch_ecc_persist_fwd(SpgEccPersistFwd p, hipStream_t stream, int* err
     *err = -1;
     return true;
   }
-  char* buf = px_acquire(p.groups, p.R, stream);
-  if (buf == nullptr) return false;
-  p.ctl = (unsigned*)buf;
-  p.gran = (unsigned long long*)(buf + SPG_PX_CTL_BYTES);
-  const int mg = px_max_group(p.groups), wpc = mg <= SPG_PX_WG_NODES ? 1 : 2;
-  p.node_wgs = spg_cdiv(mg, 4);
-  p.gran_nodes = SPG_PX_MAX_NODES;
-  if (spg_px_is_multi(p.groups.n, mg)) {      // more nodes than wavefronts: iteration-major, no head (the caller was told: head_done stays false)
+  SpgPxPlan pl;
+  if (!px_prepare(p, false, SpgPxHeadFacts{false, false, 0}, stream, &pl)) return false;
+  const dim3 grid(pl.node_wgs);
+  if (pl.form == SPG_PX_ITER_MAJOR) {      // more nodes than wavefronts: no head (the caller was told: head_done stays false)
     if (p.head.W != nullptr) { spg_set_error("persistent ECC forward: no head above %d nodes in one round", SPG_PX_MAX_NODES); *err = -1; return true; }
-    const int wpc_m = px_multi_wpc(p.matrix != 0, false);      // (the forward needs 168 registers and 52 KB of LDS: three workgroups per CU on gfx950)
-    if (wpc_m < 1 || (long)4 * px_multi_wgs(mg, wpc_m) * SPG_PX_MULTI_NPW < mg) return false;      // not resident enough: the per-iteration launches
-    p.node_wgs = px_multi_wgs(mg, wpc_m);
-    p.gran_nodes = mg;
     p.fsave = nullptr;
-    if (p.matrix) hipLaunchKernelGGL(spg_ecc_persist_fwd_multi_kernel<true>, dim3(p.node_wgs), dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL(spg_ecc_persist_fwd_multi_kernel<false>, dim3(p.node_wgs), dim3(256), 0, stream, p);
-    hipError_t e2 = hipGetLastError();
-    if (e2 != hipSuccess) { spg_set_error("persistent ECC forward launch failed: %s", hipGetErrorString(e2)); *err = (int)e2; }
-    return true;
-  }
-  const dim3 grid(p.node_wgs);
-  if (p.groups.n == 1) { if (p.matrix) px_launch_fwd<true, false>(p, wpc, grid, stream); else px_launch_fwd<false, false>(p, wpc, grid, stream); }
-  else { if (p.matrix) px_launch_fwd<true, true>(p, wpc, grid, stream); else px_launch_fwd<false, true>(p, wpc, grid, stream); }
+    if (p.matrix) hipLaunchKernelGGL(spg_ecc_persist_fwd_multi_kernel<true>, grid, dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL(spg_ecc_persist_fwd_multi_kernel<false>, grid, dim3(256), 0, stream, p);
+  } else if (p.groups.n == 1) { if (p.matrix) px_launch_fwd<true, false>(p, pl.wpc, grid, stream); else px_launch_fwd<false, false>(p, pl.wpc, grid, stream); }
+  else { if (p.matrix) px_launch_fwd<true, true>(p, pl.wpc, grid, stream); else px_launch_fwd<false, true>(p, pl.wpc, grid, stream); }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { spg_set_error("persistent ECC forward launch failed: %s", hipGetErrorString(e)); *err = (int)e; }
   return true;
@@ -2211,44 +2167,20 @@ bool spg_launch_ecc_persist_fwd(SpgEccPersistFwd p, hipStream_t stream, int* err
 bool spg_launch_ecc_persist_bwd(SpgEccPersistBwd p, hipStream_t stream, int* err, bool* head_wgrad_done) {
   *err = 0;
   if (head_wgrad_done != nullptr) *head_wgrad_done = false;
-  char* buf = px_acquire(p.groups, p.R, stream);
-  if (buf == nullptr) return false;
-  p.ctl = (unsigned*)buf;
-  p.gran = (unsigned long long*)(buf + SPG_PX_CTL_BYTES);
-  const int mg = px_max_group(p.groups), wpc = mg <= SPG_PX_WG_NODES ? 1 : 2;
-  p.node_wgs = spg_cdiv(mg, 4);
-  p.n_wgrad = 0;
-  p.gran_nodes = SPG_PX_MAX_NODES;
-  if (spg_px_is_multi(p.groups.n, mg)) {
-    const int wpc_m = px_multi_wpc(p.matrix != 0, true);
-    if (wpc_m < 1 || (long)4 * px_multi_wgs(mg, wpc_m) * SPG_PX_MULTI_NPW < mg) return false;      // not resident enough: the per-iteration launches
-    p.node_wgs = px_multi_wgs(mg, wpc_m);
-    p.gran_nodes = mg;
+  const bool wgrad = p.head.dW != nullptr && head_wgrad_done != nullptr && p.head.C <= 16 && !spg_tune_get(SPG_TUNE_NO_HEAD_SERVICE) &&
+                     (((uintptr_t)p.states | (uintptr_t)p.head.dW) & 15) == 0 && (p.ldS & 3) == 0;
+  SpgPxPlan pl;
+  if (!px_prepare(p, true, SpgPxHeadFacts{p.head.W != nullptr, wgrad, p.head.nin}, stream, &pl)) return false;
+  p.n_wgrad = pl.n_wgrad;
+  if (pl.n_wgrad > 0) *head_wgrad_done = true;
+  const dim3 grid(pl.node_wgs + pl.service);
+  if (pl.form == SPG_PX_ITER_MAJOR) {
     p.fsave = nullptr; p.fsave_tag = nullptr;
     memset(&p.head, 0, sizeof(p.head));
-    if (p.matrix) hipLaunchKernelGGL(spg_ecc_persist_bwd_multi_kernel<true>, dim3(p.node_wgs), dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL(spg_ecc_persist_bwd_multi_kernel<false>, dim3(p.node_wgs), dim3(256), 0, stream, p);
-    hipError_t e2 = hipGetLastError();
-    if (e2 != hipSuccess) { spg_set_error("persistent ECC backward launch failed: %s", hipGetErrorString(e2)); *err = (int)e2; }
-    return true;
-  }
-  int service = 0;
-  if (p.head.W != nullptr) {
-    const int spare = px_spare_wgs(p.node_wgs, wpc);
-    if (spare >= 1) service = 1;                                     // the loss
-    if (spare >= 1 && p.head.dW != nullptr && head_wgrad_done != nullptr && p.head.C <= 16 && !spg_tune_get(SPG_TUNE_NO_HEAD_SERVICE) &&
-        (((uintptr_t)p.states | (uintptr_t)p.head.dW) & 15) == 0 && (p.ldS & 3) == 0) {
-      // the classifier's parameter gradients: every wave of up to three service workgroups takes 64-column blocks
-      const int nb = (p.head.nin + 63) / 64;
-      service = spare < 3 ? spare : 3;
-      while (service > 1 && 4 * (service - 1) >= nb) --service;
-      p.n_wgrad = service;
-      *head_wgrad_done = true;
-    }
-  }
-  const dim3 grid(p.node_wgs + service);
-  if (p.groups.n == 1) { if (p.matrix) px_launch_bwd<true, false>(p, wpc, grid, stream); else px_launch_bwd<false, false>(p, wpc, grid, stream); }
-  else { if (p.matrix) px_launch_bwd<true, true>(p, wpc, grid, stream); else px_launch_bwd<false, true>(p, wpc, grid, stream); }
+    if (p.matrix) hipLaunchKernelGGL(spg_ecc_persist_bwd_multi_kernel<true>, grid, dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL(spg_ecc_persist_bwd_multi_kernel<false>, grid, dim3(256), 0, stream, p);
+  } else if (p.groups.n == 1) { if (p.matrix) px_launch_bwd<true, false>(p, pl.wpc, grid, stream); else px_launch_bwd<false, false>(p, pl.wpc, grid, stream); }
+  else { if (p.matrix) px_launch_bwd<true, true>(p, pl.wpc, grid, stream); else px_launch_bwd<false, true>(p, pl.wpc, grid, stream); }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { spg_set_error("persistent ECC backward launch failed: %s", hipGetErrorString(e)); *err = (int)e; }
   return true;

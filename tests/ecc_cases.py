@@ -28,7 +28,7 @@ so E = 1202 whatever n is.  What each rung guards (csrc/spg_ecc.hip):
   31 | 32 | 33      SPG_PX_CH = 32: one gather pass / a second one;   63 | 64 | 65: two passes / a third;   100: four passes
 The out-degree ladder guards the same constants in the backward (odeg, rev_eid) and the insertion sort of spg_graph_revsort_kernel.
 Sizes: n = 200 and 1008 (persistent launch, one workgroup per CU; 1008 = 4 (256 - 4) is the largest graph whose 252 workgroups the
-residency bound of px_acquire admits on the 256 CUs of an MI355X, and its last workgroup is full), 1024 (inside the band 1009 .. 1024
+residency bound of spg_px_plan admits on the 256 CUs of an MI355X, and its last workgroup is full), 1024 (inside the band 1009 .. 1024
 that the launcher sends to the PER-ITERATION launches on this part: 256 workgroups exceed the bound and two per CU start at 1025 only),
 1025 (two per CU: KMAX 6 / 2), 2049 (one group above 2048 nodes: the iteration-major kernels; at this size a wavefront owns one node
 in the forward and at most two in the backward -- SPG_PX_MULTI_NPW = 8 nodes per wavefront are reached only by the bit-identity tests

@@ -18,12 +18,12 @@ c. THE RECURRENT MODULE (graphnet.GraphNetwork) in training mode against oracle.
    at 1025 nodes) and is listed as that; two per CU at n = 1025; the iteration-major kernels at n = 2049 (one node per wavefront in the
    forward, at most two in the backward at this size; more nodes per wavefront: tests/test_gpu_ecc_persistent.py at 5000 and 10000
    nodes); three scenes with `parts` (two rounds, two workgroups per CU, the ladder in the second).  The library has no query for the
-   kernel that ran.  launch_form() restates the conditions that depend on the case and the device -- the cell, key 8, the rounds of
-   spg_px_plan_groups, the workgroups per CU of spg_launch_ecc_persist_{fwd,bwd} and the RESIDENCY bound of px_acquire,
-   ceil(largest round / 4) <= workgroups per CU * (CUs - 4), from torch.cuda.get_device_properties -- and every test asserts that it
-   gives the form the case is listed under.  px_acquire's other reasons to decline cannot be observed from outside: more than 15
-   iterations (none here), another stream still busy with a persistent launch (the tests use one stream), a failed allocation of
-   the 64 MiB exchange buffer.  The tests further assert that key 8 held the intended value during the run and that
+   kernel that ran.  launch_form() restates, for the case and the device (the cell, key 8, the CUs from
+   torch.cuda.get_device_properties), the plan of csrc/spg_px_plan.h -- spg_px_plan_groups and spg_px_plan, the one place that
+   decides the form, swept on the host by tests/px_plan_host_test.cpp -- and every test asserts that it gives the form the case is
+   listed under.  The launchers' other reasons to decline cannot be observed from outside: more than 15 iterations (none here),
+   an iteration-major kernel that gets fewer workgroups per CU than it was written for, another stream still busy with a persistent
+   launch (the tests use one stream), a failed allocation of the 64 MiB exchange buffer.  The tests further assert that key 8 held the intended value during the run and that
    spg_ecc_persistent_status reports no time-out and no withheld update.  Compared per element under conftest.assert_elementwise: out
    (against the reference with its own decisions), the input gradient and every parameter gradient that conftest.noise_grad does not
    exclude (against the float64 backward run with the DEVICE's filter-network ReLU decisions, which may differ from the reference's own
