@@ -90,6 +90,21 @@ int spg_lstm_cell_bwd(const float* input, const float* h, const float* c, const 
                       float* grad_h, float* grad_c, float* const* grads, float* scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The same two cells at any supported width: hidden = input = nc in {8, 16, 32, 64, 128} (nc = 32 runs the entries above).
+ * cell: 0 = GRUCellEx, 1 = LSTMCellEx.  params / grads: 6 pointers {weight_ih [G nc, nc], weight_hh [G nc, nc], bias_ih [G nc],
+ * bias_hh [G nc], ig.weight [nc, nc], ig.bias [nc]}, G = 3 (GRU) / 4 (LSTM), weights 16-byte aligned.  GRU: c, cy, grad_cy and
+ * grad_c are ignored (NULL).  scratch: >= spg_cell_scratch_floats(cell, nc, n) floats (0: refused); the forward at nc != 32
+ * uses none (NULL).  Any other width returns -2 and spg_last_error() names the supported set.  spg_cell_block_nodes: rows per workgroup of the kernels at that width (tests).
+ * ---------------------------------------------------------------------------------------------- */
+size_t spg_cell_scratch_floats(int cell, int nc, int n_rows);
+int spg_cell_block_nodes(int nc);
+int spg_cell_fwd(int cell, int nc, const float* input, const float* h, const float* c, int n_rows, const float* const* params,
+                 int layernorm, int ingate, float* hy, float* cy, float* scratch, void* stream);
+int spg_cell_bwd(int cell, int nc, const float* input, const float* h, const float* c, const float* grad_hy, const float* grad_cy,
+                 int n_rows, const float* const* params, int layernorm, int ingate, float* grad_input, float* grad_h,
+                 float* grad_c, float* const* grads, float* scratch, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused dense layer on the MFMA row-GEMM core (replaces nn.Linear / nn.Conv1d(k=1) + the preceding
  * BatchNorm/ReLU, e.g. learning/graphnet.py:47-49):  Y = act(X * in_scale + in_shift) @ W^T + bias.
  * X [M, ldx] (first K columns used), W [N, K], in_scale / in_shift [K] or NULL, Y [M, ldy].
@@ -199,7 +214,8 @@ int spg_gn_backward_ext(const spg_gn_cfg* cfg, int B, const float* clouds, const
  * params / grads groups (6 pointers each, as above): fnet linear layers [0..n_fnet) (the BatchNorm
  * after layer `bnidx` lives in that layer's group), then one group for the cell:
  *   {weight_ih, weight_hh, bias_ih, bias_hh, ig.weight, ig.bias}.
- * h0 [N, nc] (nc must be 32), edgefeats [E, fnet_widths[0]]; out [N, nc*(nrepeats+1)] (cat_all) or [N, nc].
+ * h0 [N, nc] (nc in {8, 16, 32, 64, 128}; matrix filters up to nc = 64; anything else returns -2 and spg_last_error() names the
+ * limit; the one-launch recurrence and spg_train_step serve nc = 32 only), edgefeats [E, fnet_widths[0]]; out [N, nc*(nrepeats+1)] (cat_all) or [N, nc].
  * ---------------------------------------------------------------------------------------------- */
 #define SPG_MAX_PARTS 64
 typedef struct spg_eccrnn_cfg {
@@ -208,7 +224,7 @@ typedef struct spg_eccrnn_cfg {
   int fnet_widths[SPG_MAX_LAYERS + 1];  /* n_fnet + 1 entries: input width ... output width */
   int bnidx, llbias;
   float bn_eps, bn_momentum;
-  int cell;                             /* 0: GRUCellEx (gru_*), 1: LSTMCellEx (lstm_*; weights [128,32], cx starts at 0,
+  int cell;                             /* 0: GRUCellEx (gru_*), 1: LSTMCellEx (lstm_*; weights [4 nc, nc], cx starts at 0,
                                            learning/modules.py:168-169) */
   /* Per-batch hint (0 = unknown): the batched graph's nodes [part_ptr[k], part_ptr[k+1]) , k < n_parts, are closed under
    * edges -- the scenes of a batch (learning/spg.py:178-193 concatenates them with node offsets).  With it the

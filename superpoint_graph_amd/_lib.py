@@ -89,6 +89,10 @@ SIGNATURES = {
     'spg_lstm_scratch_floats': (_sz, [_i]),
     'spg_lstm_cell_fwd': (_i, [_p, _p, _p, _i, c_void_pp, _i, _i, _p, _p, _p, _p]),
     'spg_lstm_cell_bwd': (_i, [_p, _p, _p, _p, _p, _i, c_void_pp, _i, _i, _p, _p, _p, c_void_pp, _p, _p]),
+    'spg_cell_scratch_floats': (_sz, [_i, _i, _i]),
+    'spg_cell_block_nodes': (_i, [_i]),
+    'spg_cell_fwd': (_i, [_i, _i, _p, _p, _p, _i, c_void_pp, _i, _i, _p, _p, _p, _p]),
+    'spg_cell_bwd': (_i, [_i, _i, _p, _p, _p, _p, _p, _i, c_void_pp, _i, _i, _p, _p, _p, c_void_pp, _p, _p]),
     'spg_linear_fwd': (_i, [_p, _l, _i, _i, _p, _p, _i, _p, _p, _i, _p, _l, _p]),
     'spg_linear_dgrad': (_i, [_p, _l, _i, _i, _p, _i, _p, _l, _p]),
     'spg_colsum': (_i, [_p, _l, _l, _i, _p, _p, _p]),

@@ -397,6 +397,92 @@ extern "C" int spg_lstm_cell_bwd(const float* input, const float* h, const float
 }
 
 // ---------------------------------------------------------------------------------------------
+// stand-alone GRUCellEx / LSTMCellEx at any supported width (nc = 32: the entries above; 8, 16, 64, 128: spg_ecc_wide.hip)
+// ---------------------------------------------------------------------------------------------
+// scratch layout (floats), nc != 32: dgi n*G | dgh n*G | dui n*G | duh n*G (GRU only) | dpre n*nc | xg n*nc | wgrad work, G = 3 nc / 4 nc
+static int cell_check(int cell, int nc, const char* what) {
+  SPG_CHECK_ARG(cell == SPG_CELL_GRU || cell == SPG_CELL_LSTM, "cell must be 0 (GRU) or 1 (LSTM)");
+  return spg_wide_check(nc, 0, what);
+}
+
+extern "C" size_t spg_cell_scratch_floats(int cell, int nc, int n) {
+  if (cell_check(cell, nc, "spg_cell_scratch_floats") != 0 || n <= 0) return 0;
+  if (nc == 32) return cell == SPG_CELL_LSTM ? spg_lstm_scratch_floats(n) : spg_gru_scratch_floats(n);
+  const int G = (cell == SPG_CELL_LSTM ? 4 : 3) * nc;
+  return (size_t)n * ((cell == SPG_CELL_LSTM ? 2 : 4) * G + 2 * nc) + spg_wgrad_workspace_floats(n, G, nc) + 256;
+}
+
+extern "C" int spg_cell_block_nodes(int nc) { return spg_wide_block_nodes(nc); }
+
+extern "C" int spg_cell_fwd(int cell, int nc, const float* input, const float* h, const float* c, int n, const float* const* params,
+                            int layernorm, int ingate, float* hy, float* cy, float* scratch, void* stream) {
+  SPG_TRY(cell_check(cell, nc, "spg_cell_fwd"));
+  if (nc == 32)
+    return cell == SPG_CELL_LSTM ? spg_lstm_cell_fwd(input, h, c, n, params, layernorm, ingate, hy, cy, scratch, stream)
+                                 : spg_gru_cell_fwd(input, h, n, params, layernorm, ingate, hy, scratch, stream);
+  SPG_CHECK_ARG(input && h && params && hy && n > 0 && (cell == SPG_CELL_GRU || cy), "null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  SpgEccStepFwd p; memset(&p, 0, sizeof(p));
+  SPG_TRY(gru_pack(params, layernorm, ingate, scratch, p.gru, st));
+  p.g.N = n; p.agg_in = input; p.ldagg = nc; p.hin = h; p.hout = hy; p.ld = nc; p.do_gru = 1;
+  p.cell = cell; p.cin = c; p.cout = cy;
+  return spg_launch_ecc_step_fwd_wide(p, nc, st);
+}
+
+extern "C" int spg_cell_bwd(int cell, int nc, const float* input, const float* h, const float* c, const float* grad_hy,
+                            const float* grad_cy, int n, const float* const* params, int layernorm, int ingate, float* grad_input,
+                            float* grad_h, float* grad_c, float* const* grads, float* scratch, void* stream) {
+  SPG_TRY(cell_check(cell, nc, "spg_cell_bwd"));
+  if (nc == 32) {
+    if (cell == SPG_CELL_LSTM)
+      return spg_lstm_cell_bwd(input, h, c, grad_hy, grad_cy, n, params, layernorm, ingate, grad_input, grad_h, grad_c, grads, scratch, stream);
+    return spg_gru_cell_bwd(input, h, grad_hy, n, params, layernorm, ingate, grad_input, grad_h, grads, scratch, stream);
+  }
+  const bool lstm = cell == SPG_CELL_LSTM;
+  SPG_CHECK_ARG(input && h && params && grad_input && grad_h && grads && scratch && n > 0, "null pointer");
+  SPG_CHECK_ARG(lstm ? grad_c != nullptr : grad_hy != nullptr, "null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  SpgEccStepBwd p; memset(&p, 0, sizeof(p));
+  SPG_TRY(gru_pack(params, layernorm, ingate, scratch, p.gru, st));
+  const int G = (lstm ? 4 : 3) * nc;
+  float* f = scratch;
+  float* dgi = f; f += (size_t)n * G;
+  float* dgh = f; f += (size_t)n * G;
+  float *dui = nullptr, *duh = nullptr;
+  if (!lstm) { dui = f; f += (size_t)n * G; duh = f; f += (size_t)n * G; }
+  float* dpre = f; f += (size_t)n * nc;
+  float* xg = f; f += (size_t)n * nc;
+  float* work = f;
+  p.g.N = n;   // invdeg == nullptr: no degree scaling
+  p.dcat = grad_hy; p.ldc = nc; p.dhdir = grad_h; p.use_dhdir = 0;
+  p.hin = h; p.ld = nc; p.agg = input; p.ldagg = nc; p.Gcur = grad_input; p.ldg = nc;
+  p.dgi = dgi; p.dgh = dgh; p.dui = dui; p.duh = duh; p.ld96 = G; p.dpre = dpre; p.xg = xg; p.ld32 = nc;
+  p.cell = cell;
+  if (lstm) {
+    p.cin = c; p.dcdir = grad_c; p.use_dcdir = 0;
+    if (grad_cy != nullptr) {     // the incoming cell-state gradient enters through the in/out buffer
+      hipError_t e = hipMemcpyAsync(grad_c, grad_cy, (size_t)n * nc * sizeof(float), hipMemcpyDeviceToDevice, st);
+      if (e != hipSuccess) { spg_set_error("hipMemcpyAsync: %s", hipGetErrorString(e)); return (int)e; }
+      p.use_dcdir = 1;
+    }
+  }
+  SPG_TRY(spg_launch_ecc_step_bwd_wide(p, nc, st));
+  SpgWgradParams w; memset(&w, 0, sizeof(w));
+  w.M = n; w.N = G; w.K = nc;
+  if (grads[0]) { w.a = spg_op_ident(dgi, G); w.b = spg_op_ident(xg, nc); SPG_TRY(spg_launch_wgrad(w, grads[0], work, st)); }
+  if (grads[1]) { w.a = spg_op_ident(dgh, G); w.b = spg_op_ident(h, nc); SPG_TRY(spg_launch_wgrad(w, grads[1], work, st)); }
+  // GRU: the biases are added behind the row normalisation; LSTM: in front of it
+  if (grads[2]) SPG_TRY(spg_launch_colsum(lstm ? dgi : dui, G, n, G, grads[2], work, st));
+  if (grads[3]) SPG_TRY(spg_launch_colsum(lstm ? dgh : duh, G, n, G, grads[3], work, st));
+  if (ingate) {
+    w.N = nc;
+    if (grads[4]) { w.a = spg_op_ident(dpre, nc); w.b = spg_op_ident(h, nc); SPG_TRY(spg_launch_wgrad(w, grads[4], work, st)); }
+    if (grads[5]) SPG_TRY(spg_launch_colsum(dpre, nc, n, nc, grads[5], work, st));
+  }
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
 // fused dense layer
 // ---------------------------------------------------------------------------------------------
 static SpgOperand affine_operand(const float* X, long ld, int K, const float* sc, const float* sh, int relu) {

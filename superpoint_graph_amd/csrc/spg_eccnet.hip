@@ -17,8 +17,9 @@ namespace {
 struct Plan {
   spg_eccrnn_cfg cfg;
   int N = 0, E = 0, R = 0, nout = 0;
-  long ldS = 0;                 // (R+1)*32
-  int GW = 96;                  // gate rows of the cell: 96 (GRU) / 128 (LSTM)
+  int nc = 32;                  // state width: 32 (the kernels of spg_ecc.hip) or 8, 16, 64, 128 (spg_ecc_wide.hip)
+  long ldS = 0;                 // (R+1)*nc
+  int GW = 96;                  // gate rows of the cell: 3 nc (GRU) / 4 nc (LSTM)
   bool lstm = false;
   bool training = false;
   std::vector<SpgDenseLayer> F;
@@ -37,15 +38,15 @@ struct Plan {
 int make_plan(const spg_eccrnn_cfg* cfg, int N, int E, int training, void* ws, const void* const* params, Plan& pl) {
   SPG_CHECK_ARG(cfg != nullptr && N > 0 && E >= 0, "cfg / N / E");
   const spg_eccrnn_cfg& c = *cfg;
-  SPG_CHECK_ARG(c.nc == 32, "the fused RNN-ECC path needs 32 channels");
+  SPG_TRY(spg_wide_check(c.nc, c.matrix, "the fused RNN-ECC path"));
   SPG_CHECK_ARG(c.nrepeats >= 1, "nrepeats >= 1");
   SPG_CHECK_ARG(c.n_fnet >= 1 && c.n_fnet <= SPG_MAX_LAYERS, "n_fnet");
   SPG_CHECK_ARG(c.bnidx < c.n_fnet - 1 || c.bnidx < 0, "BatchNorm after the last filter layer is not supported");
   SPG_CHECK_ARG(c.cell == SPG_CELL_GRU || c.cell == SPG_CELL_LSTM, "cell must be 0 (GRU) or 1 (LSTM)");
   pl.cfg = c; pl.N = N; pl.E = E; pl.R = c.nrepeats; pl.training = training != 0;
-  pl.lstm = c.cell == SPG_CELL_LSTM; pl.GW = pl.lstm ? 128 : 96;
-  pl.ldS = (long)(pl.R + 1) * 32;
-  pl.nout = c.matrix ? 1024 : 32;
+  pl.lstm = c.cell == SPG_CELL_LSTM; pl.nc = c.nc; pl.GW = (pl.lstm ? 4 : 3) * pl.nc;
+  pl.ldS = (long)(pl.R + 1) * pl.nc;
+  pl.nout = c.matrix ? pl.nc * pl.nc : pl.nc;
   SPG_CHECK_ARG(c.fnet_widths[c.n_fnet] == pl.nout, "filter network output width must be nc*nc (matrix) or nc (vector)");
   SpgCarver cv(ws);
   pl.F.assign(c.n_fnet, SpgDenseLayer());
@@ -77,13 +78,14 @@ int make_plan(const spg_eccrnn_cfg* cfg, int N, int E, int training, void* ws, c
     SPG_CHECK_ARG(!c.ingate || (pl.gru.w_ig && pl.gru.b_ig), "missing input-gate parameters");
   }
   pl.gru.layernorm = c.layernorm; pl.gru.ingate = c.ingate;
+  SPG_CHECK_ARG(pl.nc == 32 || (((uintptr_t)pl.gru.w_ih | (uintptr_t)pl.gru.w_hh | (uintptr_t)pl.gru.w_ig) & 15) == 0, "RNN cell weights must be 16-byte aligned");
   pl.states = cv.take<float>((size_t)N * pl.ldS);
   pl.agg = cv.take<float>((size_t)N * pl.ldS);
   if (pl.lstm) pl.cells = cv.take<float>((size_t)N * pl.ldS);
   // persistent GRU recurrence in training: the forward keeps the cell's internals of every (node, iteration) for the backward
   // (12 x 64 floats each: 31 MB per 1000 nodes x 10 iterations) instead of the backward recomputing them on its critical path
   pl.fsave = nullptr; pl.fsave_tag = nullptr;
-  pl.px = !pl.lstm && c.n_parts >= 0 && c.n_parts <= SPG_MAX_PARTS && spg_px_plan_groups(N, c.n_parts, c.part_ptr, spg_tune_get(SPG_TUNE_NO_PERSIST_ECC), &pl.groups);
+  pl.px = pl.nc == 32 && !pl.lstm && c.n_parts >= 0 && c.n_parts <= SPG_MAX_PARTS && spg_px_plan_groups(N, c.n_parts, c.part_ptr, spg_tune_get(SPG_TUNE_NO_PERSIST_ECC), &pl.groups);
   // (more nodes than wavefronts -- one round above SPG_PX_MAX_NODES nodes: the backward recomputes the cell instead, spg_ecc.hip)
   if (pl.px && pl.training && !spg_px_groups_multi(pl.groups)) {
     pl.fsave_tag = cv.take<unsigned>(64);
@@ -114,13 +116,14 @@ struct BwdScratch {
 void carve_bwd(const Plan& pl, void* ws, BwdScratch& s) {
   SpgCarver cv(ws);
   const size_t rows = (size_t)pl.N * (pl.R + 1);
-  s.G = cv.take<float>(rows * 32);
+  const size_t nc = pl.nc;
+  s.G = cv.take<float>(rows * nc);
   s.dgi = cv.take<float>(rows * pl.GW); s.dgh = cv.take<float>(rows * pl.GW);
-  if (!pl.lstm) { s.dui = cv.take<float>(rows * 96); s.duh = cv.take<float>(rows * 96); }
-  s.dpre = cv.take<float>(rows * 32); s.xg = cv.take<float>(rows * 32);
+  if (!pl.lstm) { s.dui = cv.take<float>(rows * pl.GW); s.duh = cv.take<float>(rows * pl.GW); }
+  s.dpre = cv.take<float>(rows * nc); s.xg = cv.take<float>(rows * nc);
   s.zero_bytes = cv.off;
-  s.dhdir = cv.take<float>((size_t)pl.N * 32);
-  if (pl.lstm) s.dcdir = cv.take<float>((size_t)pl.N * 32);
+  s.dhdir = cv.take<float>((size_t)pl.N * nc);
+  if (pl.lstm) s.dcdir = cv.take<float>((size_t)pl.N * nc);
   const size_t Er = pl.E > 0 ? pl.E : 1;
   s.dWts = cv.take<float>(Er * pl.nout);
   int cmax = 4;
@@ -131,7 +134,7 @@ void carve_bwd(const Plan& pl, void* ws, BwdScratch& s) {
     workmax += spg_queue_layer_floats((long)Er, l.cout, l.cin);
   }
   // GRU: three weight gradients + three bias column sums over all (node, iteration) rows
-  const size_t work2max = 16 + 3 * spg_queue_layer_floats((long)rows, pl.GW, 32);
+  const size_t work2max = 16 + 3 * spg_queue_layer_floats((long)rows, pl.GW, pl.nc);
   int hmax = 4;   // widest hidden activation
   for (int i = 0; i + 1 < (int)pl.F.size(); ++i) hmax = pl.F[i].cout > hmax ? pl.F[i].cout : hmax;
   s.dzA = cv.take<float>(Er * hmax); s.dzB = cv.take<float>(Er * hmax);
@@ -218,23 +221,24 @@ static int eccrnn_recurrent_forward(Plan& pl, const void* graph_ws, const float*
       return err;
     }
   }
+  const int nc = pl.nc;
   if (sc != nullptr) {      // per-iteration launches read a materialised descriptor matrix
-    SPG_TRY(spg_gather_rows(sc->emb, 32, sc->slot_of_row, N, 32, sc->desc, 32, (void*)st));
+    SPG_TRY(spg_gather_rows(sc->emb, nc, sc->slot_of_row, N, nc, sc->desc, nc, (void*)st));
     h0 = sc->desc;
   }
   if (pl.fsave_tag != nullptr) SPG_TRY(spg_zero_bytes_async(pl.fsave_tag, sizeof(unsigned), st));      // per-iteration path: nothing was kept
-  SPG_TRY(spg_launch_copy2d(h0, 32, pl.states, pl.ldS, N, 32, st));
+  SPG_TRY(spg_launch_copy2d(h0, nc, pl.states, pl.ldS, N, nc, st));
   for (int r = 0; r < pl.R; ++r) {
     SpgEccStepFwd p; memset(&p, 0, sizeof(p));
     p.g = gr; p.W = pl.F.back().y; p.matrix = pl.cfg.matrix;
-    p.hin = pl.states + (size_t)r * 32; p.hout = pl.states + (size_t)(r + 1) * 32; p.ld = pl.ldS;
-    p.agg_save = pl.training ? pl.agg + (size_t)r * 32 : nullptr; p.ldagg = pl.ldS;
+    p.hin = pl.states + (size_t)r * nc; p.hout = pl.states + (size_t)(r + 1) * nc; p.ld = pl.ldS;
+    p.agg_save = pl.training ? pl.agg + (size_t)r * nc : nullptr; p.ldagg = pl.ldS;
     p.do_gru = 1; p.gru = pl.gru; p.cell = pl.cfg.cell;
-    if (pl.lstm) { p.cin = r > 0 ? pl.cells + (size_t)r * 32 : nullptr; p.cout = pl.cells + (size_t)(r + 1) * 32; }
-    SPG_TRY(spg_launch_ecc_step_fwd(p, st));
+    if (pl.lstm) { p.cin = r > 0 ? pl.cells + (size_t)r * nc : nullptr; p.cout = pl.cells + (size_t)(r + 1) * nc; }
+    SPG_TRY(nc == 32 ? spg_launch_ecc_step_fwd(p, st) : spg_launch_ecc_step_fwd_wide(p, nc, st));
   }
   if (pl.cfg.cat_all) SPG_TRY(spg_launch_copy2d(pl.states, pl.ldS, out, pl.ldS, N, (int)pl.ldS, st));
-  else SPG_TRY(spg_launch_copy2d(pl.states + (size_t)pl.R * 32, pl.ldS, out, 32, N, 32, st));
+  else SPG_TRY(spg_launch_copy2d(pl.states + (size_t)pl.R * nc, pl.ldS, out, nc, N, nc, st));
   return 0;
 }
 
@@ -317,20 +321,21 @@ void eccrnn_backward_tail_stages(std::shared_ptr<BwdCtx> c, std::vector<SpgStage
     Plan& pl = c->pl; BwdScratch& s = c->s;
     const int R = pl.R, GW = pl.GW, rows = pl.N * (R + 1);
     SpgWgradParams w; memset(&w, 0, sizeof(w));
-    w.a = spg_op_ident(s.dgi, GW); w.b = spg_op_ident(s.xg, 32); w.M = rows; w.N = GW; w.K = 32;
+    const int nc = pl.nc;
+    w.a = spg_op_ident(s.dgi, GW); w.b = spg_op_ident(s.xg, nc); w.M = rows; w.N = GW; w.K = nc;
     SPG_TRY(spg_queue_wgrad(c->rq2, w, pl.cell_grads[0], st));
-    w.a = spg_op_ident(s.dgh, GW); w.b = spg_op_ident(pl.states, 32);
+    w.a = spg_op_ident(s.dgh, GW); w.b = spg_op_ident(pl.states, nc);
     SPG_TRY(spg_queue_wgrad(c->rq2, w, pl.cell_grads[1], st));
     // GRU: the biases are added behind the row normalisation; LSTM: in front of it
     SPG_TRY(spg_queue_colsum(c->rq2, pl.lstm ? s.dgi : s.dui, GW, rows, GW, pl.cell_grads[2], st));
     SPG_TRY(spg_queue_colsum(c->rq2, pl.lstm ? s.dgh : s.duh, GW, rows, GW, pl.cell_grads[3], st));
     if (pl.cfg.ingate) {
-      w.a = spg_op_ident(s.dpre, 32); w.b = spg_op_ident(pl.states, 32); w.N = 32;
+      w.a = spg_op_ident(s.dpre, nc); w.b = spg_op_ident(pl.states, nc); w.N = nc;
       // the input gate's bias gradient = column sums of dpre: as their own small job, not riding along with the weight
       // gradient -- the body that carries them needs more than 128 registers and would push the whole group (2700 small
       // workgroups) to the 2-workgroups-per-CU build of the grouped kernel (spg_gemm.hip)
       SPG_TRY(spg_queue_wgrad(c->rq2, w, pl.cell_grads[4], st));
-      SPG_TRY(spg_queue_colsum(c->rq2, s.dpre, 32, rows, 32, pl.cell_grads[5], st));
+      SPG_TRY(spg_queue_colsum(c->rq2, s.dpre, nc, rows, nc, pl.cell_grads[5], st));
     }
     return 0;
   };
@@ -356,7 +361,8 @@ void eccrnn_backward_tail_stages(std::shared_ptr<BwdCtx> c, std::vector<SpgStage
       return 0;
     }
     // per-edge filter gradients (sum over the iterations): the head of the filter network's chain
-    SPG_TRY(spg_launch_ecc_edge_wgrad(c->gr, pl.cfg.matrix, pl.states, ldS, s.G, ldS, R, s.dWts, st));
+    if (pl.nc == 32) SPG_TRY(spg_launch_ecc_edge_wgrad(c->gr, pl.cfg.matrix, pl.states, ldS, s.G, ldS, R, s.dWts, st));
+    else SPG_TRY(spg_launch_ecc_edge_wgrad_wide(c->gr, pl.cfg.matrix, pl.nc, pl.states, ldS, s.G, ldS, R, s.dWts, st));      // (its own launch, in stream order)
     c->cur = spg_op_ident(s.dWts, pl.nout);
     return 0;
   });
@@ -417,7 +423,7 @@ int spg_eccrnn_backward_phase(const spg_eccrnn_cfg* cfg, int N, int E, const voi
   memset(&c->pending, 0, sizeof(c->pending));
   SpgGraph& gr = c->gr;
   const int R = pl.R;
-  const int GW = pl.GW;
+  const int GW = pl.GW, nc = pl.nc;
   const long ldS = pl.ldS, ld96 = (long)(R + 1) * GW;
   // ---- back-propagation through the R iterations ----
   bool persistent = false;
@@ -445,19 +451,19 @@ int spg_eccrnn_backward_phase(const spg_eccrnn_cfg* cfg, int N, int E, const voi
   for (int r = R - 1; r >= 0 && !persistent; --r) {
     SpgEccStepBwd p; memset(&p, 0, sizeof(p));
     p.g = gr; p.W = pl.F.back().y; p.matrix = pl.cfg.matrix;
-    if (pl.cfg.cat_all) { p.dcat = grad_out + (size_t)(r + 1) * 32; p.ldc = ldS; }
-    else if (r == R - 1) { p.dcat = grad_out; p.ldc = 32; }
-    p.Gnext = r < R - 1 ? s.G + (size_t)(r + 1) * 32 : nullptr; p.ldg = ldS;
+    if (pl.cfg.cat_all) { p.dcat = grad_out + (size_t)(r + 1) * nc; p.ldc = ldS; }
+    else if (r == R - 1) { p.dcat = grad_out; p.ldc = nc; }
+    p.Gnext = r < R - 1 ? s.G + (size_t)(r + 1) * nc : nullptr; p.ldg = ldS;
     p.dhdir = s.dhdir; p.use_dhdir = r < R - 1;
-    p.hin = pl.states + (size_t)r * 32; p.ld = ldS;
-    p.agg = pl.agg + (size_t)r * 32; p.ldagg = ldS;
-    p.Gcur = s.G + (size_t)r * 32;
+    p.hin = pl.states + (size_t)r * nc; p.ld = ldS;
+    p.agg = pl.agg + (size_t)r * nc; p.ldagg = ldS;
+    p.Gcur = s.G + (size_t)r * nc;
     p.dgi = s.dgi + (size_t)r * GW; p.dgh = s.dgh + (size_t)r * GW; p.ld96 = ld96;
-    if (!pl.lstm) { p.dui = s.dui + (size_t)r * 96; p.duh = s.duh + (size_t)r * 96; }
-    p.dpre = s.dpre + (size_t)r * 32; p.xg = s.xg + (size_t)r * 32; p.ld32 = ldS;
+    if (!pl.lstm) { p.dui = s.dui + (size_t)r * GW; p.duh = s.duh + (size_t)r * GW; }
+    p.dpre = s.dpre + (size_t)r * nc; p.xg = s.xg + (size_t)r * nc; p.ld32 = ldS;
     p.gru = pl.gru; p.cell = pl.cfg.cell;
-    if (pl.lstm) { p.cin = r > 0 ? pl.cells + (size_t)r * 32 : nullptr; p.dcdir = s.dcdir; p.use_dcdir = r < R - 1; }
-    SPG_TRY(spg_launch_ecc_step_bwd(p, st));
+    if (pl.lstm) { p.cin = r > 0 ? pl.cells + (size_t)r * nc : nullptr; p.dcdir = s.dcdir; p.use_dcdir = r < R - 1; }
+    SPG_TRY(nc == 32 ? spg_launch_ecc_step_bwd(p, st) : spg_launch_ecc_step_bwd_wide(p, nc, st));
   }
   if (!persistent) {
     SpgEccStepBwd p; memset(&p, 0, sizeof(p));
@@ -465,10 +471,10 @@ int spg_eccrnn_backward_phase(const spg_eccrnn_cfg* cfg, int N, int E, const voi
     if (pl.cfg.cat_all) { p.dcat = grad_out; p.ldc = ldS; }
     p.Gnext = s.G; p.ldg = ldS; p.dhdir = s.dhdir; p.use_dhdir = 1; p.gx = grad_h0; p.final_only = 1;
     p.gru = pl.gru; p.cell = pl.cfg.cell;
-    SPG_TRY(spg_launch_ecc_step_bwd(p, st));
+    SPG_TRY(nc == 32 ? spg_launch_ecc_step_bwd(p, st) : spg_launch_ecc_step_bwd_wide(p, nc, st));
   }
-  if (sc != nullptr && !persistent)       // per-iteration launches wrote grad_h0 [N, 32]: gather the embeddable rows
-    SPG_TRY(spg_gather_rows(grad_h0, 32, sc->idx_valid, sc->B, 32, sc->grad_emb, 32, stream));
+  if (sc != nullptr && !persistent)       // per-iteration launches wrote grad_h0 [N, nc]: gather the embeddable rows
+    SPG_TRY(spg_gather_rows(grad_h0, nc, sc->idx_valid, sc->B, nc, sc->grad_emb, nc, stream));
   // ---- the tail: nothing below depends on it, it depends on nothing but the recurrence's outputs ----
   std::vector<SpgStage> stages;
   eccrnn_backward_tail_stages(c, stages, std::move(extra_leaf));

@@ -40,7 +40,7 @@ extern "C" int spg_train_step(const spg_step_args* a, void* stream) {
   SPG_CHECK_ARG(a != nullptr, "null arguments");
   SPG_CHECK_ARG(a->ptn_cfg && a->ecc_cfg && a->B > 0 && a->N > 0 && a->E >= 0, "cfg / sizes");
   SPG_CHECK_ARG(a->clouds && a->ptn_params && a->ptn_grads && a->ptn_ws && a->ptn_bwd_ws && a->emb && a->grad_emb, "PointNet buffers");
-  SPG_CHECK_ARG(a->slot_of_row && a->idx_valid && a->desc && a->grad_desc && a->nf == a->ecc_cfg->nc, "scatter buffers / embedding width");
+  SPG_CHECK_ARG(a->slot_of_row && a->idx_valid && a->desc && a->grad_desc && a->nf == a->ecc_cfg->nc && a->ecc_cfg->nc == 32, "scatter buffers / embedding width (the fused step serves 32 channels)");
   SPG_CHECK_ARG(a->graph_ws && a->ecc_params && a->ecc_grads && a->ecc_ws && a->ecc_bwd_ws && a->ecc_out && a->grad_ecc_out, "RNN-ECC buffers");
   SPG_CHECK_ARG(a->cls_W && a->cls_dW && a->cls_work && a->logits && a->grad_logits && a->nout > 0 && (a->nout & 3) == 0 && a->n_classes > 0, "classifier buffers");
   SPG_CHECK_ARG(a->target && a->loss_buf, "loss buffers");
@@ -112,7 +112,7 @@ extern "C" int spg_infer_step(const spg_step_args* a, void* stream) {
   SPG_CHECK_ARG(a != nullptr, "null arguments");
   SPG_CHECK_ARG(a->ptn_cfg && a->ecc_cfg && a->B > 0 && a->N > 0 && a->E >= 0, "cfg / sizes");
   SPG_CHECK_ARG(a->clouds && a->ptn_params && a->ptn_ws && a->emb, "PointNet buffers");
-  SPG_CHECK_ARG(a->slot_of_row && a->idx_valid && a->desc && a->nf == a->ecc_cfg->nc, "scatter buffers / embedding width");
+  SPG_CHECK_ARG(a->slot_of_row && a->idx_valid && a->desc && a->nf == a->ecc_cfg->nc && a->ecc_cfg->nc == 32, "scatter buffers / embedding width (the fused step serves 32 channels)");
   SPG_CHECK_ARG(a->graph_ws && a->ecc_params && a->ecc_ws && a->ecc_out, "RNN-ECC buffers");
   SPG_CHECK_ARG(a->cls_W && a->logits && a->nout > 0 && (a->nout & 3) == 0 && a->n_classes > 0, "classifier buffers");
   SPG_CHECK_ARG(spg_riders_pending() == 0, "a rider chain is already registered on this thread");

@@ -9,7 +9,8 @@ from . import _layers
 
 class _CellEx:
     """What GRUCellEx and LSTMCellEx add to torch's cells: row normalisation of the gate pre-activations and an input gate
-    (same parameters as the reference: weight_ih, weight_hh, bias_ih, bias_hh, ig.*), 32 channels on the HIP kernels."""
+    (same parameters as the reference: weight_ih, weight_hh, bias_ih, bias_hh, ig.*); the HIP kernels serve hidden = input in
+    ops.model.CELL_WIDTHS (8, 16, 32, 64, 128) with bias."""
 
     def __init__(self, input_size, hidden_size, bias=True, layernorm=True, ingate=True):
         super().__init__(input_size, hidden_size, bias)
@@ -27,9 +28,16 @@ class _CellEx:
     def _autograd_params(self, input):
         if not input.is_cuda:
             raise RuntimeError(f'superpoint_graph_amd.{type(self).__name__} has no CPU path')
-        if self.input_size != 32 or self.hidden_size != 32 or self.bias_ih is None:
-            raise NotImplementedError(f'the HIP {self._KIND} cell is specialised for 32 channels with bias')
+        self._check_supported()
         return [p for p in self.param_tensors() if p is not None]
+
+    def _check_supported(self):
+        """NotImplementedError, before any launch, for what the HIP cells do not serve; the message names what they do."""
+        if self.input_size != self.hidden_size or self.bias_ih is None:
+            raise NotImplementedError(f'the HIP {self._KIND} cell needs input_size == hidden_size and bias=True (got input_size '
+                                      f'{self.input_size}, hidden_size {self.hidden_size}, bias {self.bias_ih is not None}); '
+                                      f'supported widths: {", ".join(map(str, ops.model.CELL_WIDTHS))}')
+        ops.model.check_cell_width(self.hidden_size, what=f'the HIP {self._KIND} cell')
 
     def __repr__(self):
         s = super().__repr__() + '('
@@ -53,13 +61,18 @@ class _GRUCellFunction(torch.autograd.Function):
     def forward(ctx, cell, input, hidden, *params):
         ctx.cell = cell
         ctx.save_for_backward(input, hidden)
+        if cell.hidden_size != 32:
+            return ops.model.cell_fwd('gru', input, hidden, None, cell.param_tensors(), cell._layernorm, cell._ingate)[0]
         return ops.gru_cell_fwd(input, hidden, cell.param_tensors(), cell._layernorm, cell._ingate)
 
     @staticmethod
     def backward(ctx, grad_out):
         input, hidden = ctx.saved_tensors
         cell = ctx.cell
-        gi, gh, grads = ops.gru_cell_bwd(input, hidden, grad_out, cell.param_tensors(), cell._layernorm, cell._ingate)
+        if cell.hidden_size != 32:
+            gi, gh, _, grads = ops.model.cell_bwd('gru', input, hidden, None, grad_out, None, cell.param_tensors(), cell._layernorm, cell._ingate)
+        else:
+            gi, gh, grads = ops.gru_cell_bwd(input, hidden, grad_out, cell.param_tensors(), cell._layernorm, cell._ingate)
         return (None, gi, gh) + tuple(g for g in grads if g is not None)
 
 
@@ -78,14 +91,16 @@ class _LSTMCellFunction(torch.autograd.Function):
     def forward(ctx, cell, input, h, c, *params):
         ctx.cell = cell
         ctx.save_for_backward(input, h, c)
+        if cell.hidden_size != 32:
+            return ops.model.cell_fwd('lstm', input, h, c, cell.param_tensors(), cell._layernorm, cell._ingate)
         return ops.lstm_cell_fwd(input, h, c, cell.param_tensors(), cell._layernorm, cell._ingate)
 
     @staticmethod
     def backward(ctx, grad_hy, grad_cy):
         input, h, c = ctx.saved_tensors
         cell = ctx.cell
-        gi, gh, gc, grads = ops.lstm_cell_bwd(input, h, c, grad_hy, grad_cy, cell.param_tensors(), cell._layernorm,
-                                              cell._ingate)
+        bwd = ops.lstm_cell_bwd if cell.hidden_size == 32 else (lambda *a: ops.model.cell_bwd('lstm', *a))
+        gi, gh, gc, grads = bwd(input, h, c, grad_hy, grad_cy, cell.param_tensors(), cell._layernorm, cell._ingate)
         return (None, gi, gh, gc) + tuple(g for g in grads if g is not None)
 
 
@@ -157,7 +172,8 @@ class _EccRnnFunction(torch.autograd.Function):
 class RNNGraphConvModule(nn.Module):
     """Recurrent graph convolution: filter-generating network once, then nrepeats x {ECC, RNN cell}
     (reference learning/modules.py:128-183; same constructor signature, `_cell` / `_fnet` attribute names).
-    With a GRUCellEx / LSTMCellEx cell and 32 channels the whole module is one C call (spg_eccrnn_forward)."""
+    With a GRUCellEx / LSTMCellEx cell of a supported width (ops.model.CELL_WIDTHS; matrix filters up to 64) the whole module is one C
+    call (spg_eccrnn_forward); the one-launch recurrence serves 32 channels, the other widths run one launch per iteration."""
     _spg_kernel_grads = True      # FlatParameters: the HIP backward writes the gradient views of filter network and cell
 
     def __init__(self, cell, filter_net, nfeat=None, vv=True, gc_info=None, nrepeats=1, cat_all=False,
@@ -212,6 +228,8 @@ class RNNGraphConvModule(nn.Module):
         widths = [fg[0][0].in_features] + [lin.out_features for lin, _ in fg]
         nc = self._cell.hidden_size
         matrix = widths[-1] == nc * nc and widths[-1] != nc
+        self._cell._check_supported()      # the cell's own refusals (width, input_size, bias)
+        ops.model.check_cell_width(nc, matrix, 'the fused RNN-ECC path')
         bn = next((b for _, b in fg if b is not None), None)
         if bn is not None:
             _layers.bn_momentum(bn)
@@ -227,10 +245,10 @@ class RNNGraphConvModule(nn.Module):
         idxn, idxe, degs, degs_gpu, edgefeats = self._gci.get_buffers()
         if idxe is not None:
             raise NotImplementedError('filter sharing (idxe) is not supported by the fused RNN-ECC path')
+        cfg, rows = self._cfg_and_groups()      # (first: refuses an unsupported width before anything is launched)
         if self.training:
             _layers.advance_batch_counters(self._fnet)
         graph = self._gci.device_graph()
-        cfg, rows = self._cfg_and_groups()
         cfg = self._cfg_for(cfg, self._gci, graph.N)
         return _EccRnnFunction.apply(self, cfg, rows, hx, edgefeats.contiguous().float(), graph, self.training,
                                      *_layers.node_inputs(self, rows, hx.device))

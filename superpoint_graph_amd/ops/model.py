@@ -132,6 +132,76 @@ def lstm_cell_bwd(inp, h, c, grad_hy, grad_cy, params, layernorm: bool, ingate: 
 
 
 # --------------------------------------------------------------------------------------------------
+# GRU / LSTM cell at any supported width (spg_cell_fwd / spg_cell_bwd; 32 runs the kernels of the entries above)
+# --------------------------------------------------------------------------------------------------
+CELL_KINDS = {'gru': 0, 'lstm': 1}
+CELL_WIDTHS = (8, 16, 32, 64, 128)            # state widths the HIP cells and the RNN-ECC recurrence serve
+MATRIX_FILTER_MAX_WIDTH = 64                  # [E, nc, nc] filters: 64 KB per edge at 128 are refused
+
+
+def check_cell_width(nc, matrix=False, what='the HIP RNN-ECC kernels'):
+    """NotImplementedError that names the supported set, before anything is launched (the library refuses the same with -2)."""
+    if nc not in CELL_WIDTHS:
+        raise NotImplementedError(f'{what}: state width {nc} is not supported; supported widths: {", ".join(map(str, CELL_WIDTHS))}')
+    if matrix and nc > MATRIX_FILTER_MAX_WIDTH:
+        raise NotImplementedError(f'{what}: matrix filters at state width {nc} ({nc * nc * 4 // 1024} KB of filter per edge) are not supported; '
+                                  f'matrix filters are limited to widths up to {MATRIX_FILTER_MAX_WIDTH} (use vector filters at {nc})')
+
+
+def _cell_check(rc, what):
+    if rc == -2:
+        raise NotImplementedError(lib().spg_last_error().decode())
+    check(rc, what)
+
+
+def _cell_scratch(kind, nc, n, device):
+    floats = lib().spg_cell_scratch_floats(CELL_KINDS[kind], nc, n)
+    if floats == 0:
+        _cell_check(-2, 'spg_cell_scratch_floats')
+    return torch.empty(floats, dtype=torch.float32, device=device)
+
+
+def cell_block_nodes(nc: int) -> int:
+    """Rows (nodes) per workgroup of the cell / step kernels at width nc."""
+    return int(lib().spg_cell_block_nodes(nc))
+
+
+def cell_fwd(kind, inp, h, c, params: Sequence[Optional[torch.Tensor]], layernorm: bool, ingate: bool):
+    """GRUCellEx / LSTMCellEx forward at width nc = inp.shape[1]: -> (hy, cy); c and cy are None for the GRU."""
+    _req(inp, torch.float32, 'input'); _req(h, torch.float32, 'hidden')
+    n, nc = inp.shape
+    check_cell_width(nc, what=f'the HIP {kind.upper()} cell')
+    if tuple(h.shape) != (n, nc):
+        raise ValueError(f'hidden must be [{n}, {nc}], got {tuple(h.shape)}')
+    lstm = kind == 'lstm'
+    if lstm:
+        _req(c, torch.float32, 'hidden[1]')
+    hy = torch.empty_like(h)
+    cy = torch.empty_like(h) if lstm else None
+    scratch = _cell_scratch(kind, nc, n, inp.device) if nc == 32 else None      # (the wide forward needs none; the 32-wide entries ask for theirs)
+    _cell_check(lib().spg_cell_fwd(CELL_KINDS[kind], nc, _ptr(inp), _ptr(h), _ptr(c) if lstm else None, n, _ptr_array(params),
+                                   int(layernorm), int(ingate), _ptr(hy), _ptr(cy), _ptr(scratch), _stream()), 'spg_cell_fwd')
+    return hy, cy
+
+
+def cell_bwd(kind, inp, h, c, grad_hy, grad_cy, params, layernorm: bool, ingate: bool):
+    """-> (grad input, grad h, grad c or None, parameter gradients like `params`)."""
+    n, nc = inp.shape
+    check_cell_width(nc, what=f'the HIP {kind.upper()} cell')
+    lstm = kind == 'lstm'
+    grad_hy = None if grad_hy is None else _req(grad_hy.contiguous(), torch.float32, 'grad_hy')
+    grad_cy = None if (grad_cy is None or not lstm) else _req(grad_cy.contiguous(), torch.float32, 'grad_cy')
+    gi, gh = torch.empty_like(inp), torch.empty_like(h)
+    gc = torch.empty_like(h) if lstm else None
+    grads = [None if p is None else torch.empty_like(p) for p in params]
+    scratch = _cell_scratch(kind, nc, n, inp.device)
+    _cell_check(lib().spg_cell_bwd(CELL_KINDS[kind], nc, _ptr(inp), _ptr(h), _ptr(c) if lstm else None, _ptr(grad_hy), _ptr(grad_cy), n,
+                                   _ptr_array(params), int(layernorm), int(ingate), _ptr(gi), _ptr(gh), _ptr(gc), _ptr_array(grads),
+                                   _ptr(scratch), _stream()), 'spg_cell_bwd')
+    return gi, gh, gc, grads
+
+
+# --------------------------------------------------------------------------------------------------
 # dense layer
 # --------------------------------------------------------------------------------------------------
 def linear_fwd(x, w, bias=None, in_scale=None, in_shift=None, in_relu=False):
@@ -404,6 +474,7 @@ def gn_backward(state: GroupNormState, groups, grad_emb, want_clouds=False):
 # --------------------------------------------------------------------------------------------------
 def make_eccrnn_cfg(nc, nrepeats, matrix, layernorm, ingate, cat_all, fnet_widths, bnidx, llbias, bn_eps=1e-5,
                     bn_momentum=0.1, cell='gru') -> EccRnnCfg:
+    check_cell_width(nc, bool(matrix), 'the fused RNN-ECC path')
     c = EccRnnCfg()
     c.nc, c.nrepeats, c.matrix, c.layernorm, c.ingate, c.cat_all = nc, nrepeats, int(matrix), int(layernorm), int(ingate), int(cat_all)
     c.n_fnet = len(fnet_widths) - 1
