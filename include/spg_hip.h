@@ -64,37 +64,16 @@ int spg_ecc_aggregate_bwd(int dtype, const void* x, const void* w, const int64_t
                           void* grad_x, void* grad_w, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * GRUCellEx.forward / backward (learning/modules.py:224-251), hidden = input = 32 channels.
- * params: 6 pointers {weight_ih [96,32], weight_hh [96,32], bias_ih [96], bias_hh [96],
- * ig.weight [32,32], ig.bias [32]} (the last two may be NULL when ingate == 0).
- * scratch: >= spg_gru_scratch_floats(n) floats.  grads: 6 pointers like params.
- * ---------------------------------------------------------------------------------------------- */
-size_t spg_gru_scratch_floats(int n_rows);
-int spg_gru_cell_fwd(const float* input, const float* hidden, int n_rows, const float* const* params, int layernorm,
-                     int ingate, float* out, float* scratch, void* stream);
-int spg_gru_cell_bwd(const float* input, const float* hidden, const float* grad_out, int n_rows,
-                     const float* const* params, int layernorm, int ingate, float* grad_input, float* grad_hidden,
-                     float* const* grads, float* scratch, void* stream);
-
-/* ------------------------------------------------------------------------------------------------
- * LSTMCellEx.forward / backward (learning/modules.py:280-309), hidden = input = 32 channels.
- * params: 6 pointers {weight_ih [128,32], weight_hh [128,32], bias_ih [128], bias_hh [128], ig.weight [32,32],
- * ig.bias [32]}.  hidden = (h, c); outputs hy, cy.  Backward takes the gradients wrt hy and cy (either may be NULL =
- * zero) and returns the gradients wrt input, h and c.  scratch: >= spg_lstm_scratch_floats(n) floats.
- * ---------------------------------------------------------------------------------------------- */
-size_t spg_lstm_scratch_floats(int n_rows);
-int spg_lstm_cell_fwd(const float* input, const float* h, const float* c, int n_rows, const float* const* params,
-                      int layernorm, int ingate, float* hy, float* cy, float* scratch, void* stream);
-int spg_lstm_cell_bwd(const float* input, const float* h, const float* c, const float* grad_hy, const float* grad_cy,
-                      int n_rows, const float* const* params, int layernorm, int ingate, float* grad_input,
-                      float* grad_h, float* grad_c, float* const* grads, float* scratch, void* stream);
-
-/* ------------------------------------------------------------------------------------------------
- * The same two cells at any supported width: hidden = input = nc in {8, 16, 32, 64, 128} (nc = 32 runs the entries above).
- * cell: 0 = GRUCellEx, 1 = LSTMCellEx.  params / grads: 6 pointers {weight_ih [G nc, nc], weight_hh [G nc, nc], bias_ih [G nc],
- * bias_hh [G nc], ig.weight [nc, nc], ig.bias [nc]}, G = 3 (GRU) / 4 (LSTM), weights 16-byte aligned.  GRU: c, cy, grad_cy and
- * grad_c are ignored (NULL).  scratch: >= spg_cell_scratch_floats(cell, nc, n) floats (0: refused); the forward at nc != 32
- * uses none (NULL).  Any other width returns -2 and spg_last_error() names the supported set.  spg_cell_block_nodes: rows per workgroup of the kernels at that width (tests).
+ * GRUCellEx.forward / backward (learning/modules.py:224-251) and LSTMCellEx.forward / backward (:280-309), stand-alone:
+ * hidden = input = nc channels, nc in {8, 16, 32, 64, 128}.  Any other width returns -2 (spg_cell_scratch_floats: 0) and
+ * spg_last_error() names the supported set.
+ * cell: 0 = GRUCellEx, 1 = LSTMCellEx; G = 3 (GRU) / 4 (LSTM).  params / grads: 6 pointers {weight_ih [G nc, nc],
+ * weight_hh [G nc, nc], bias_ih [G nc], bias_hh [G nc], ig.weight [nc, nc], ig.bias [nc]} (the last two may be NULL when
+ * ingate == 0; a NULL in grads: not wanted), weights 16-byte aligned.
+ * LSTM: hidden = (h, c), outputs hy, cy; c may be NULL (zeros).  The backward takes the gradients wrt hy and cy (either may be
+ * NULL = zero) and returns the gradients wrt input, h and c.  GRU: c, cy, grad_cy and grad_c are ignored (NULL).
+ * scratch: the backward needs >= spg_cell_scratch_floats(cell, nc, n_rows) floats; the forward uses none (NULL is accepted).
+ * spg_cell_block_nodes: rows per workgroup of the kernels at that width (tests).
  * ---------------------------------------------------------------------------------------------- */
 size_t spg_cell_scratch_floats(int cell, int nc, int n_rows);
 int spg_cell_block_nodes(int nc);
@@ -103,6 +82,20 @@ int spg_cell_fwd(int cell, int nc, const float* input, const float* h, const flo
 int spg_cell_bwd(int cell, int nc, const float* input, const float* h, const float* c, const float* grad_hy, const float* grad_cy,
                  int n_rows, const float* const* params, int layernorm, int ingate, float* grad_input, float* grad_h,
                  float* grad_c, float* const* grads, float* scratch, void* stream);
+/* the same call with cell = 0 (GRU) and nc = 32 fixed: spg_gru_scratch_floats(n) = spg_cell_scratch_floats(0, 32, n) */
+size_t spg_gru_scratch_floats(int n_rows);
+int spg_gru_cell_fwd(const float* input, const float* hidden, int n_rows, const float* const* params, int layernorm,
+                     int ingate, float* out, float* scratch, void* stream);
+int spg_gru_cell_bwd(const float* input, const float* hidden, const float* grad_out, int n_rows,
+                     const float* const* params, int layernorm, int ingate, float* grad_input, float* grad_hidden,
+                     float* const* grads, float* scratch, void* stream);
+/* ... and with cell = 1 (LSTM) and nc = 32 fixed */
+size_t spg_lstm_scratch_floats(int n_rows);
+int spg_lstm_cell_fwd(const float* input, const float* h, const float* c, int n_rows, const float* const* params,
+                      int layernorm, int ingate, float* hy, float* cy, float* scratch, void* stream);
+int spg_lstm_cell_bwd(const float* input, const float* h, const float* c, const float* grad_hy, const float* grad_cy,
+                      int n_rows, const float* const* params, int layernorm, int ingate, float* grad_input,
+                      float* grad_h, float* grad_c, float* const* grads, float* scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Fused dense layer on the MFMA row-GEMM core (replaces nn.Linear / nn.Conv1d(k=1) + the preceding

@@ -273,190 +273,88 @@ extern "C" int spg_ecc_aggregate_bwd(int dtype, const void* x, const void* w, co
 }
 
 // ---------------------------------------------------------------------------------------------
-// stand-alone GRUCellEx
+// stand-alone GRUCellEx / LSTMCellEx, hidden = input = nc in {8, 16, 32, 64, 128}: the step kernels with agg_in / dcat
+// (spg_ecc_step_fwd / spg_ecc_step_bwd, spg_ecc.h), then the parameter gradients.  G = 3 nc (GRU) / 4 nc (LSTM) gate rows.
 // ---------------------------------------------------------------------------------------------
-// scratch layout (floats): w_ih_t 3072 | w_hh_t 3072 | w_ig_t 1024 | dgi n*96 | dgh n*96 | dui n*96 | duh n*96 |
-//                          dpre n*32 | xg n*32 | G n*32 | dhdir n*32 | wgrad work
-static size_t gru_work_floats(int n) { return spg_wgrad_workspace_floats(n, 96, 32); }
-extern "C" size_t spg_gru_scratch_floats(int n) { return 7168 + (size_t)n * (4 * 96 + 4 * 32) + gru_work_floats(n) + 64; }
+static int cell_check(int cell, int nc, const char* what) {
+  SPG_CHECK_ARG(cell == SPG_CELL_GRU || cell == SPG_CELL_LSTM, "cell must be 0 (GRU) or 1 (LSTM)");
+  return spg_wide_check(nc, 0, what);
+}
 
-static int gru_pack(const float* const* params, int layernorm, int ingate, float* scratch, SpgGruParams& G, hipStream_t st) {
+// The backward's scratch (the forward has none): the only source of its size and of every pointer into it.  base == null: size query.
+struct CellScratch {
+  float *dgi, *dgh;      // [n, G] gradients wrt the gate pre-activations in front of the row normalisation
+  float *dui, *duh;      // [n, G] ... behind it, where the GRU adds its biases (LSTM: null, its biases sit in front)
+  float *dpre, *xg;      // [n, nc] gradient wrt the input gate's pre-activation; the gated input
+  float* work;           // split partials of one weight gradient / column sum at a time
+  size_t floats;
+};
+
+static CellScratch cell_scratch(int cell, int nc, int n, float* base) {
+  const bool lstm = cell == SPG_CELL_LSTM;
+  const int G = (lstm ? 4 : 3) * nc;
+  const size_t rows = n > 0 ? n : 0;
+  SpgCarver cv(base);      // (256-byte steps: more than the 16 bytes the vector loads of spg_launch_wgrad ask for)
+  CellScratch s;
+  s.dgi = cv.take<float>(rows * G); s.dgh = cv.take<float>(rows * G);
+  s.dui = lstm ? nullptr : cv.take<float>(rows * G);
+  s.duh = lstm ? nullptr : cv.take<float>(rows * G);
+  s.dpre = cv.take<float>(rows * nc); s.xg = cv.take<float>(rows * nc);
+  // the [G, nc] weight gradients and the input gate's [nc, nc] one split their rows differently: room for the larger plan
+  const size_t wg = spg_wgrad_workspace_floats(n, G, nc), wi = spg_wgrad_workspace_floats(n, nc, nc);
+  s.work = cv.take<float>(wg > wi ? wg : wi);
+  s.floats = cv.off / sizeof(float);
+  return s;
+}
+
+extern "C" size_t spg_cell_scratch_floats(int cell, int nc, int n) {
+  if (cell_check(cell, nc, "spg_cell_scratch_floats") != 0 || n <= 0) return 0;
+  return cell_scratch(cell, nc, n, nullptr).floats;
+}
+extern "C" size_t spg_gru_scratch_floats(int n) { return cell_scratch(SPG_CELL_GRU, 32, n, nullptr).floats; }
+extern "C" size_t spg_lstm_scratch_floats(int n) { return cell_scratch(SPG_CELL_LSTM, 32, n, nullptr).floats; }
+
+extern "C" int spg_cell_block_nodes(int nc) { return spg_wide_block_nodes(nc); }
+
+static int cell_bind_params(const float* const* params, int layernorm, int ingate, SpgGruParams& G) {
   memset(&G, 0, sizeof(G));
   G.w_ih = params[0]; G.w_hh = params[1]; G.b_ih = params[2]; G.b_hh = params[3]; G.w_ig = params[4]; G.b_ig = params[5];
   SPG_CHECK_ARG(G.w_ih && G.w_hh && G.b_ih && G.b_hh, "missing GRU parameters");
   SPG_CHECK_ARG(!ingate || (G.w_ig && G.b_ig), "missing input-gate parameters");
   G.layernorm = layernorm; G.ingate = ingate;
   SPG_CHECK_ARG((((uintptr_t)G.w_ih | (uintptr_t)G.w_hh | (uintptr_t)G.w_ig) & 15) == 0, "GRU weights must be 16-byte aligned");
-  (void)scratch; (void)st;
   return 0;
 }
 
-extern "C" int spg_gru_cell_fwd(const float* input, const float* hidden, int n, const float* const* params, int layernorm,
-                                int ingate, float* out, float* scratch, void* stream) {
-  SPG_CHECK_ARG(input && hidden && params && out && scratch && n > 0, "null pointer");
-  hipStream_t st = (hipStream_t)stream;
+// c (LSTM) may be null: zeros
+static int cell_fwd_impl(int cell, int nc, const float* input, const float* h, const float* c, int n, const float* const* params,
+                         int layernorm, int ingate, float* hy, float* cy, void* stream) {
+  const bool lstm = cell == SPG_CELL_LSTM;
+  SPG_CHECK_ARG(input && h && params && hy && n > 0 && (!lstm || cy), "null pointer");
   SpgEccStepFwd p; memset(&p, 0, sizeof(p));
-  SPG_TRY(gru_pack(params, layernorm, ingate, scratch, p.gru, st));
-  p.g.N = n; p.agg_in = input; p.ldagg = 32; p.hin = hidden; p.hout = out; p.ld = 32; p.do_gru = 1;
-  return spg_launch_ecc_step_fwd(p, st);
-}
-
-extern "C" int spg_gru_cell_bwd(const float* input, const float* hidden, const float* grad_out, int n,
-                                const float* const* params, int layernorm, int ingate, float* grad_input,
-                                float* grad_hidden, float* const* grads, float* scratch, void* stream) {
-  SPG_CHECK_ARG(input && hidden && grad_out && params && grad_input && grad_hidden && grads && scratch && n > 0,
-                "null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  SpgEccStepBwd p; memset(&p, 0, sizeof(p));
-  SPG_TRY(gru_pack(params, layernorm, ingate, scratch, p.gru, st));
-  float* f = scratch + 7168;
-  float* dgi = f; f += (size_t)n * 96;
-  float* dgh = f; f += (size_t)n * 96;
-  float* dui = f; f += (size_t)n * 96;
-  float* duh = f; f += (size_t)n * 96;
-  float* dpre = f; f += (size_t)n * 32;
-  float* xg = f; f += (size_t)n * 32;
-  f += (size_t)n * 64;   // (G, dhdir written straight to the outputs)
-  float* work = f;
-  p.g.N = n;   // invdeg == nullptr: no degree scaling
-  p.dcat = grad_out; p.ldc = 32; p.dhdir = grad_hidden; p.use_dhdir = 0;
-  p.hin = hidden; p.ld = 32; p.agg = input; p.ldagg = 32; p.Gcur = grad_input; p.ldg = 32;
-  p.dgi = dgi; p.dgh = dgh; p.dui = dui; p.duh = duh; p.ld96 = 96; p.dpre = dpre; p.xg = xg; p.ld32 = 32;
-  SPG_TRY(spg_launch_ecc_step_bwd(p, st));
-  SpgWgradParams w; memset(&w, 0, sizeof(w));
-  w.M = n; w.N = 96; w.K = 32;
-  if (grads[0]) { w.a = spg_op_ident(dgi, 96); w.b = spg_op_ident(xg, 32); SPG_TRY(spg_launch_wgrad(w, grads[0], work, st)); }
-  if (grads[1]) { w.a = spg_op_ident(dgh, 96); w.b = spg_op_ident(hidden, 32); SPG_TRY(spg_launch_wgrad(w, grads[1], work, st)); }
-  if (grads[2]) SPG_TRY(spg_launch_colsum(dui, 96, n, 96, grads[2], work, st));
-  if (grads[3]) SPG_TRY(spg_launch_colsum(duh, 96, n, 96, grads[3], work, st));
-  if (ingate) {
-    w.N = 32;
-    if (grads[4]) { w.a = spg_op_ident(dpre, 32); w.b = spg_op_ident(hidden, 32); SPG_TRY(spg_launch_wgrad(w, grads[4], work, st)); }
-    if (grads[5]) SPG_TRY(spg_launch_colsum(dpre, 32, n, 32, grads[5], work, st));
-  }
-  return 0;
-}
-
-// ---------------------------------------------------------------------------------------------
-// stand-alone LSTMCellEx
-// ---------------------------------------------------------------------------------------------
-// scratch layout (floats): dgi n*128 | dgh n*128 | dpre n*32 | xg n*32 | zero n*32 | wgrad work
-extern "C" size_t spg_lstm_scratch_floats(int n) {
-  return (size_t)n * (2 * 128 + 3 * 32) + spg_wgrad_workspace_floats(n, 128, 32) + 256;
-}
-
-extern "C" int spg_lstm_cell_fwd(const float* input, const float* h, const float* c, int n, const float* const* params,
-                                 int layernorm, int ingate, float* hy, float* cy, float* scratch, void* stream) {
-  SPG_CHECK_ARG(input && h && params && hy && cy && n > 0, "null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  SpgEccStepFwd p; memset(&p, 0, sizeof(p));
-  SPG_TRY(gru_pack(params, layernorm, ingate, scratch, p.gru, st));
-  p.g.N = n; p.agg_in = input; p.ldagg = 32; p.hin = h; p.hout = hy; p.ld = 32; p.do_gru = 1;
-  p.cell = SPG_CELL_LSTM; p.cin = c; p.cout = cy;
-  return spg_launch_ecc_step_fwd(p, st);
-}
-
-extern "C" int spg_lstm_cell_bwd(const float* input, const float* h, const float* c, const float* grad_hy,
-                                 const float* grad_cy, int n, const float* const* params, int layernorm, int ingate,
-                                 float* grad_input, float* grad_h, float* grad_c, float* const* grads, float* scratch,
-                                 void* stream) {
-  SPG_CHECK_ARG(input && h && params && grad_input && grad_h && grad_c && grads && scratch && n > 0, "null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  SpgEccStepBwd p; memset(&p, 0, sizeof(p));
-  SPG_TRY(gru_pack(params, layernorm, ingate, scratch, p.gru, st));
-  float* f = scratch;
-  float* dgi = f; f += (size_t)n * 128;
-  float* dgh = f; f += (size_t)n * 128;
-  float* dpre = f; f += (size_t)n * 32;
-  float* xg = f; f += (size_t)n * 32;
-  f += (size_t)n * 32;
-  float* work = f;
-  p.g.N = n;   // invdeg == nullptr: no degree scaling
-  p.dcat = grad_hy; p.ldc = 32; p.dhdir = grad_h; p.use_dhdir = 0;
-  p.hin = h; p.ld = 32; p.agg = input; p.ldagg = 32; p.Gcur = grad_input; p.ldg = 32;
-  p.dgi = dgi; p.dgh = dgh; p.ld96 = 128; p.dpre = dpre; p.xg = xg; p.ld32 = 32;
-  p.cell = SPG_CELL_LSTM; p.cin = c; p.dcdir = grad_c; p.use_dcdir = 0;
-  if (grad_cy != nullptr) {     // the incoming cell-state gradient enters through the in/out buffer
-    hipError_t e = hipMemcpyAsync(grad_c, grad_cy, (size_t)n * 32 * sizeof(float), hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) { spg_set_error("hipMemcpyAsync: %s", hipGetErrorString(e)); return (int)e; }
-    p.use_dcdir = 1;
-  }
-  SPG_TRY(spg_launch_ecc_step_bwd(p, st));
-  SpgWgradParams w; memset(&w, 0, sizeof(w));
-  w.M = n; w.N = 128; w.K = 32;
-  if (grads[0]) { w.a = spg_op_ident(dgi, 128); w.b = spg_op_ident(xg, 32); SPG_TRY(spg_launch_wgrad(w, grads[0], work, st)); }
-  if (grads[1]) { w.a = spg_op_ident(dgh, 128); w.b = spg_op_ident(h, 32); SPG_TRY(spg_launch_wgrad(w, grads[1], work, st)); }
-  if (grads[2]) SPG_TRY(spg_launch_colsum(dgi, 128, n, 128, grads[2], work, st));
-  if (grads[3]) SPG_TRY(spg_launch_colsum(dgh, 128, n, 128, grads[3], work, st));
-  if (ingate) {
-    w.N = 32;
-    if (grads[4]) { w.a = spg_op_ident(dpre, 32); w.b = spg_op_ident(h, 32); SPG_TRY(spg_launch_wgrad(w, grads[4], work, st)); }
-    if (grads[5]) SPG_TRY(spg_launch_colsum(dpre, 32, n, 32, grads[5], work, st));
-  }
-  return 0;
-}
-
-// ---------------------------------------------------------------------------------------------
-// stand-alone GRUCellEx / LSTMCellEx at any supported width (nc = 32: the entries above; 8, 16, 64, 128: spg_ecc_wide.hip)
-// ---------------------------------------------------------------------------------------------
-// scratch layout (floats), nc != 32: dgi n*G | dgh n*G | dui n*G | duh n*G (GRU only) | dpre n*nc | xg n*nc | wgrad work, G = 3 nc / 4 nc
-static int cell_check(int cell, int nc, const char* what) {
-  SPG_CHECK_ARG(cell == SPG_CELL_GRU || cell == SPG_CELL_LSTM, "cell must be 0 (GRU) or 1 (LSTM)");
-  return spg_wide_check(nc, 0, what);
-}
-
-extern "C" size_t spg_cell_scratch_floats(int cell, int nc, int n) {
-  if (cell_check(cell, nc, "spg_cell_scratch_floats") != 0 || n <= 0) return 0;
-  if (nc == 32) return cell == SPG_CELL_LSTM ? spg_lstm_scratch_floats(n) : spg_gru_scratch_floats(n);
-  const int G = (cell == SPG_CELL_LSTM ? 4 : 3) * nc;
-  return (size_t)n * ((cell == SPG_CELL_LSTM ? 2 : 4) * G + 2 * nc) + spg_wgrad_workspace_floats(n, G, nc) + 256;
-}
-
-extern "C" int spg_cell_block_nodes(int nc) { return spg_wide_block_nodes(nc); }
-
-extern "C" int spg_cell_fwd(int cell, int nc, const float* input, const float* h, const float* c, int n, const float* const* params,
-                            int layernorm, int ingate, float* hy, float* cy, float* scratch, void* stream) {
-  SPG_TRY(cell_check(cell, nc, "spg_cell_fwd"));
-  if (nc == 32)
-    return cell == SPG_CELL_LSTM ? spg_lstm_cell_fwd(input, h, c, n, params, layernorm, ingate, hy, cy, scratch, stream)
-                                 : spg_gru_cell_fwd(input, h, n, params, layernorm, ingate, hy, scratch, stream);
-  SPG_CHECK_ARG(input && h && params && hy && n > 0 && (cell == SPG_CELL_GRU || cy), "null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  SpgEccStepFwd p; memset(&p, 0, sizeof(p));
-  SPG_TRY(gru_pack(params, layernorm, ingate, scratch, p.gru, st));
+  SPG_TRY(cell_bind_params(params, layernorm, ingate, p.gru));
   p.g.N = n; p.agg_in = input; p.ldagg = nc; p.hin = h; p.hout = hy; p.ld = nc; p.do_gru = 1;
-  p.cell = cell; p.cin = c; p.cout = cy;
-  return spg_launch_ecc_step_fwd_wide(p, nc, st);
+  p.cell = cell;
+  if (lstm) { p.cin = c; p.cout = cy; }
+  return spg_ecc_step_fwd(p, nc, (hipStream_t)stream);
 }
 
-extern "C" int spg_cell_bwd(int cell, int nc, const float* input, const float* h, const float* c, const float* grad_hy,
-                            const float* grad_cy, int n, const float* const* params, int layernorm, int ingate, float* grad_input,
-                            float* grad_h, float* grad_c, float* const* grads, float* scratch, void* stream) {
-  SPG_TRY(cell_check(cell, nc, "spg_cell_bwd"));
-  if (nc == 32) {
-    if (cell == SPG_CELL_LSTM)
-      return spg_lstm_cell_bwd(input, h, c, grad_hy, grad_cy, n, params, layernorm, ingate, grad_input, grad_h, grad_c, grads, scratch, stream);
-    return spg_gru_cell_bwd(input, h, grad_hy, n, params, layernorm, ingate, grad_input, grad_h, grads, scratch, stream);
-  }
+// grad_hy (LSTM) and grad_cy may be null: zeros
+static int cell_bwd_impl(int cell, int nc, const float* input, const float* h, const float* c, const float* grad_hy,
+                         const float* grad_cy, int n, const float* const* params, int layernorm, int ingate, float* grad_input,
+                         float* grad_h, float* grad_c, float* const* grads, float* scratch, void* stream) {
   const bool lstm = cell == SPG_CELL_LSTM;
   SPG_CHECK_ARG(input && h && params && grad_input && grad_h && grads && scratch && n > 0, "null pointer");
   SPG_CHECK_ARG(lstm ? grad_c != nullptr : grad_hy != nullptr, "null pointer");
   hipStream_t st = (hipStream_t)stream;
   SpgEccStepBwd p; memset(&p, 0, sizeof(p));
-  SPG_TRY(gru_pack(params, layernorm, ingate, scratch, p.gru, st));
+  SPG_TRY(cell_bind_params(params, layernorm, ingate, p.gru));
   const int G = (lstm ? 4 : 3) * nc;
-  float* f = scratch;
-  float* dgi = f; f += (size_t)n * G;
-  float* dgh = f; f += (size_t)n * G;
-  float *dui = nullptr, *duh = nullptr;
-  if (!lstm) { dui = f; f += (size_t)n * G; duh = f; f += (size_t)n * G; }
-  float* dpre = f; f += (size_t)n * nc;
-  float* xg = f; f += (size_t)n * nc;
-  float* work = f;
+  const CellScratch s = cell_scratch(cell, nc, n, scratch);
   p.g.N = n;   // invdeg == nullptr: no degree scaling
   p.dcat = grad_hy; p.ldc = nc; p.dhdir = grad_h; p.use_dhdir = 0;
   p.hin = h; p.ld = nc; p.agg = input; p.ldagg = nc; p.Gcur = grad_input; p.ldg = nc;
-  p.dgi = dgi; p.dgh = dgh; p.dui = dui; p.duh = duh; p.ld96 = G; p.dpre = dpre; p.xg = xg; p.ld32 = nc;
+  p.dgi = s.dgi; p.dgh = s.dgh; p.dui = s.dui; p.duh = s.duh; p.ld96 = G; p.dpre = s.dpre; p.xg = s.xg; p.ld32 = nc;
   p.cell = cell;
   if (lstm) {
     p.cin = c; p.dcdir = grad_c; p.use_dcdir = 0;
@@ -466,20 +364,61 @@ extern "C" int spg_cell_bwd(int cell, int nc, const float* input, const float* h
       p.use_dcdir = 1;
     }
   }
-  SPG_TRY(spg_launch_ecc_step_bwd_wide(p, nc, st));
+  SPG_TRY(spg_ecc_step_bwd(p, nc, st));
   SpgWgradParams w; memset(&w, 0, sizeof(w));
   w.M = n; w.N = G; w.K = nc;
-  if (grads[0]) { w.a = spg_op_ident(dgi, G); w.b = spg_op_ident(xg, nc); SPG_TRY(spg_launch_wgrad(w, grads[0], work, st)); }
-  if (grads[1]) { w.a = spg_op_ident(dgh, G); w.b = spg_op_ident(h, nc); SPG_TRY(spg_launch_wgrad(w, grads[1], work, st)); }
+  if (grads[0]) { w.a = spg_op_ident(s.dgi, G); w.b = spg_op_ident(s.xg, nc); SPG_TRY(spg_launch_wgrad(w, grads[0], s.work, st)); }
+  if (grads[1]) { w.a = spg_op_ident(s.dgh, G); w.b = spg_op_ident(h, nc); SPG_TRY(spg_launch_wgrad(w, grads[1], s.work, st)); }
   // GRU: the biases are added behind the row normalisation; LSTM: in front of it
-  if (grads[2]) SPG_TRY(spg_launch_colsum(lstm ? dgi : dui, G, n, G, grads[2], work, st));
-  if (grads[3]) SPG_TRY(spg_launch_colsum(lstm ? dgh : duh, G, n, G, grads[3], work, st));
+  if (grads[2]) SPG_TRY(spg_launch_colsum(lstm ? s.dgi : s.dui, G, n, G, grads[2], s.work, st));
+  if (grads[3]) SPG_TRY(spg_launch_colsum(lstm ? s.dgh : s.duh, G, n, G, grads[3], s.work, st));
   if (ingate) {
     w.N = nc;
-    if (grads[4]) { w.a = spg_op_ident(dpre, nc); w.b = spg_op_ident(h, nc); SPG_TRY(spg_launch_wgrad(w, grads[4], work, st)); }
-    if (grads[5]) SPG_TRY(spg_launch_colsum(dpre, nc, n, nc, grads[5], work, st));
+    if (grads[4]) { w.a = spg_op_ident(s.dpre, nc); w.b = spg_op_ident(h, nc); SPG_TRY(spg_launch_wgrad(w, grads[4], s.work, st)); }
+    if (grads[5]) SPG_TRY(spg_launch_colsum(s.dpre, nc, n, nc, grads[5], s.work, st));
   }
   return 0;
+}
+
+// ---- the exported entries: the one implementation with cell and nc as arguments, or fixed (GRU / LSTM at 32); the forwards use
+//      no scratch (null is accepted) ----
+extern "C" int spg_cell_fwd(int cell, int nc, const float* input, const float* h, const float* c, int n, const float* const* params,
+                            int layernorm, int ingate, float* hy, float* cy, float* scratch, void* stream) {
+  SPG_TRY(cell_check(cell, nc, "spg_cell_fwd"));
+  return cell_fwd_impl(cell, nc, input, h, c, n, params, layernorm, ingate, hy, cy, stream);
+}
+
+extern "C" int spg_cell_bwd(int cell, int nc, const float* input, const float* h, const float* c, const float* grad_hy,
+                            const float* grad_cy, int n, const float* const* params, int layernorm, int ingate, float* grad_input,
+                            float* grad_h, float* grad_c, float* const* grads, float* scratch, void* stream) {
+  SPG_TRY(cell_check(cell, nc, "spg_cell_bwd"));
+  return cell_bwd_impl(cell, nc, input, h, c, grad_hy, grad_cy, n, params, layernorm, ingate, grad_input, grad_h, grad_c, grads,
+                       scratch, stream);
+}
+
+extern "C" int spg_gru_cell_fwd(const float* input, const float* hidden, int n, const float* const* params, int layernorm,
+                                int ingate, float* out, float* scratch, void* stream) {
+  return cell_fwd_impl(SPG_CELL_GRU, 32, input, hidden, nullptr, n, params, layernorm, ingate, out, nullptr, stream);
+}
+
+extern "C" int spg_gru_cell_bwd(const float* input, const float* hidden, const float* grad_out, int n,
+                                const float* const* params, int layernorm, int ingate, float* grad_input,
+                                float* grad_hidden, float* const* grads, float* scratch, void* stream) {
+  return cell_bwd_impl(SPG_CELL_GRU, 32, input, hidden, nullptr, grad_out, nullptr, n, params, layernorm, ingate, grad_input,
+                       grad_hidden, nullptr, grads, scratch, stream);
+}
+
+extern "C" int spg_lstm_cell_fwd(const float* input, const float* h, const float* c, int n, const float* const* params,
+                                 int layernorm, int ingate, float* hy, float* cy, float* scratch, void* stream) {
+  return cell_fwd_impl(SPG_CELL_LSTM, 32, input, h, c, n, params, layernorm, ingate, hy, cy, stream);
+}
+
+extern "C" int spg_lstm_cell_bwd(const float* input, const float* h, const float* c, const float* grad_hy,
+                                 const float* grad_cy, int n, const float* const* params, int layernorm, int ingate,
+                                 float* grad_input, float* grad_h, float* grad_c, float* const* grads, float* scratch,
+                                 void* stream) {
+  return cell_bwd_impl(SPG_CELL_LSTM, 32, input, h, c, grad_hy, grad_cy, n, params, layernorm, ingate, grad_input, grad_h, grad_c,
+                       grads, scratch, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -137,17 +137,19 @@ int spg_launch_ecc_edge_wgrad(const SpgGraph& g, int matrix, const float* states
                               int R, float* dW, hipStream_t stream);
 int spg_launch_copy2d(const float* src, long lds, float* dst, long ldd, long rows, int cols, hipStream_t stream);
 
-// ---- state widths nc = 8, 16, 64, 128 (spg_ecc_wide.hip): the same parameter blocks with nc for every 32 above (weights
-//      [G nc, nc], dhdir / dcdir / gx [N, nc], ld96 / ld32 the leading dimensions of the G nc / nc wide per-row arrays); a
-//      workgroup owns spg_wide_block_nodes(nc) nodes.  do_gru = 0 is not served.  Matrix filters up to SPG_WIDE_MATRIX_MAX_NC.
+// ---- the three operations at any state width nc in {8, 16, 32, 64, 128} (spg_ecc_wide.hip): 32 runs the launchers above, the
+//      other widths the kernels of spg_ecc_wide.hip on the same parameter blocks with nc for every 32 above (weights [G nc, nc],
+//      dhdir / dcdir / gx [N, nc], ld96 / ld32 the leading dimensions of the G nc / nc wide per-row arrays); a workgroup owns
+//      spg_wide_block_nodes(nc) nodes.  do_gru = 0 is served at 32 only.  Matrix filters up to SPG_WIDE_MATRIX_MAX_NC.  The edge
+//      gradient joins an open grouped launch at 32 only; at the other widths it is its own launch in stream order.
 #define SPG_WIDE_MATRIX_MAX_NC 64
 // 0, or -2 with the supported set in spg_last_error(): nc outside {8, 16, 32, 64, 128}, matrix filters above the limit
 int spg_wide_check(int nc, int matrix, const char* what);
 int spg_wide_block_nodes(int nc);
-int spg_launch_ecc_step_fwd_wide(const SpgEccStepFwd& p, int nc, hipStream_t stream);
-int spg_launch_ecc_step_bwd_wide(const SpgEccStepBwd& p, int nc, hipStream_t stream);
-int spg_launch_ecc_edge_wgrad_wide(const SpgGraph& g, int matrix, int nc, const float* states, long lds, const float* G, long ldg,
-                                   int R, float* dW, hipStream_t stream);
+int spg_ecc_step_fwd(const SpgEccStepFwd& p, int nc, hipStream_t stream);
+int spg_ecc_step_bwd(const SpgEccStepBwd& p, int nc, hipStream_t stream);
+int spg_ecc_edge_wgrad(const SpgGraph& g, int matrix, int nc, const float* states, long lds, const float* G, long ldg, int R,
+                       float* dW, hipStream_t stream);
 
 // ---- persistent (one launch for all iterations) forms of the GRU recurrence, spg_ecc.hip ----
 // (the limits, the rounds and the launch plan: spg_px_plan.h)

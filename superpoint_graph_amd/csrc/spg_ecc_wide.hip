@@ -11,6 +11,8 @@
 // Expressions and their order follow the 32-wide kernels of spg_ecc.hip (reference learning/modules.py:224-251, :280-309):
 // the GRU adds its biases BEHIND the row normalisation, the LSTM in front of it.
 // No kernel here waits on another workgroup.
+// At the end of the file: the one launcher per operation for EVERY width (spg_ecc_step_fwd / _bwd, spg_ecc_edge_wgrad), whose
+// case 32 is the launcher of spg_ecc.hip.
 #include "spg_ecc.h"
 
 namespace {
@@ -278,7 +280,7 @@ __global__ __launch_bounds__(SPG_THREADS) void spg_ecc_wide_step_bwd_kernel(cons
       continue;
     }
     if (MATRIX && p.Gnext != nullptr && p.matrix) {
-      // (MATRIX is instantiated up to SPG_WIDE_MATRIX_MAX_NC = 64 only: spg_launch_ecc_step_bwd_wide refuses `matrix` at 128)
+      // (MATRIX is instantiated up to SPG_WIDE_MATRIX_MAX_NC = 64 only: launch_bwd refuses `matrix` at 128)
       if constexpr (MATRIX && NC <= 64) {      // lane = (k group, c): partial sums over the out-edges first, ONE reduction over c at the end
         constexpr int KG = 64 / NC, NQ = NC / KG;
         const int c = lane % NC, kg = lane / NC;
@@ -436,7 +438,7 @@ __global__ __launch_bounds__(SPG_THREADS) void spg_ecc_wide_edge_wgrad_kernel(co
   const float* hs = p.states + (long)p.g.src[e] * p.lds;
   const float* gd = p.G + (long)p.g.dst[e] * p.ldg;
   if (p.matrix) {
-    // (compiled out at 128: spg_launch_ecc_edge_wgrad_wide refuses `matrix` there -- dW would stay untouched)
+    // (compiled out at 128: launch_edge_wgrad refuses `matrix` there -- dW would stay untouched)
     if constexpr (NC <= 64) {      // dW_e[k][c] = sum_r h^r_src[k] g^r_dst[c]; lane = (k group, c)
       constexpr int KG = 64 / NC, NQ = NC / KG;
       const int c = lane % NC, kg = lane / NC;
@@ -463,6 +465,8 @@ __global__ __launch_bounds__(SPG_THREADS) void spg_ecc_wide_edge_wgrad_kernel(co
 
 template <int NC>
 int launch_fwd(const SpgEccStepFwd& p, hipStream_t stream) {
+  SPG_CHECK_ARG(p.do_gru, "the wide forward step always runs the cell");
+  SPG_CHECK_ARG(!(p.matrix && NC > SPG_WIDE_MATRIX_MAX_NC) || p.agg_in != nullptr, "matrix filters at this width");
   const dim3 grid(spg_cdiv(p.g.N, WideBlock<NC>::NB));
   if (p.cell == SPG_CELL_LSTM) hipLaunchKernelGGL((spg_ecc_wide_step_fwd_kernel<NC, SPG_CELL_LSTM>), grid, dim3(SPG_THREADS), 0, stream, p);
   else hipLaunchKernelGGL((spg_ecc_wide_step_fwd_kernel<NC, SPG_CELL_GRU>), grid, dim3(SPG_THREADS), 0, stream, p);
@@ -481,10 +485,19 @@ int launch_bwd_m(const SpgEccStepBwd& p, hipStream_t stream) {
 
 template <int NC>
 int launch_bwd(const SpgEccStepBwd& p, hipStream_t stream) {
+  SPG_CHECK_ARG(!(p.matrix && NC > SPG_WIDE_MATRIX_MAX_NC) || p.Gnext == nullptr, "matrix filters at this width");
   if constexpr (NC <= SPG_WIDE_MATRIX_MAX_NC) {
     if (p.matrix && p.Gnext != nullptr) return launch_bwd_m<NC, true>(p, stream);
   }
   return launch_bwd_m<NC, false>(p, stream);
+}
+
+template <int NC>
+int launch_edge_wgrad(const SpgEdgeWgrad& p, hipStream_t stream) {      // (its own launch, in stream order; E > 0)
+  SPG_CHECK_ARG(!(p.matrix && NC > SPG_WIDE_MATRIX_MAX_NC), "matrix filters at this width");
+  hipLaunchKernelGGL(spg_ecc_wide_edge_wgrad_kernel<NC>, dim3(spg_cdiv(p.g.E, 4)), dim3(SPG_THREADS), 0, stream, p);
+  SPG_LAUNCH_CHECK();
+  return 0;
 }
 
 }  // namespace
@@ -506,51 +519,50 @@ int spg_wide_block_nodes(int nc) {
   switch (nc) {
     case 8: return WideBlock<8>::NB;
     case 16: return WideBlock<16>::NB;
+    case 32: return 4;      // the 32-wide kernels of spg_ecc.hip: one node per wavefront
     case 64: return WideBlock<64>::NB;
     case 128: return WideBlock<128>::NB;
-    default: return 4;      // the 32-wide kernels of spg_ecc.hip: one node per wavefront
+    default: return 4;      // (as before; spg_wide_check is what refuses a width)
   }
 }
 
-int spg_launch_ecc_step_fwd_wide(const SpgEccStepFwd& p, int nc, hipStream_t stream) {
-  SPG_CHECK_ARG(p.do_gru, "the wide forward step always runs the cell");
-  SPG_CHECK_ARG(!(p.matrix && nc > SPG_WIDE_MATRIX_MAX_NC) || p.agg_in != nullptr, "matrix filters at this width");
+// ---- one launcher per operation: 32 forwards to the launchers of spg_ecc.hip ----
+int spg_ecc_step_fwd(const SpgEccStepFwd& p, int nc, hipStream_t stream) {
   switch (nc) {
     case 8: return launch_fwd<8>(p, stream);
     case 16: return launch_fwd<16>(p, stream);
+    case 32: return spg_launch_ecc_step_fwd(p, stream);
     case 64: return launch_fwd<64>(p, stream);
     case 128: return launch_fwd<128>(p, stream);
-    default: SPG_CHECK_ARG(false, "wide step: nc must be 8, 16, 64 or 128");
+    default: SPG_CHECK_ARG(false, "forward step: nc must be 8, 16, 32, 64 or 128");
   }
   return 0;
 }
 
-int spg_launch_ecc_step_bwd_wide(const SpgEccStepBwd& p, int nc, hipStream_t stream) {
-  SPG_CHECK_ARG(!(p.matrix && nc > SPG_WIDE_MATRIX_MAX_NC) || p.Gnext == nullptr, "matrix filters at this width");
+int spg_ecc_step_bwd(const SpgEccStepBwd& p, int nc, hipStream_t stream) {
   switch (nc) {
     case 8: return launch_bwd<8>(p, stream);
     case 16: return launch_bwd<16>(p, stream);
+    case 32: return spg_launch_ecc_step_bwd(p, stream);
     case 64: return launch_bwd<64>(p, stream);
     case 128: return launch_bwd<128>(p, stream);
-    default: SPG_CHECK_ARG(false, "wide step: nc must be 8, 16, 64 or 128");
+    default: SPG_CHECK_ARG(false, "backward step: nc must be 8, 16, 32, 64 or 128");
   }
   return 0;
 }
 
-int spg_launch_ecc_edge_wgrad_wide(const SpgGraph& g, int matrix, int nc, const float* states, long lds, const float* G, long ldg,
-                                   int R, float* dW, hipStream_t stream) {
+int spg_ecc_edge_wgrad(const SpgGraph& g, int matrix, int nc, const float* states, long lds, const float* G, long ldg, int R,
+                       float* dW, hipStream_t stream) {
   if (g.E == 0) return 0;
-  SPG_CHECK_ARG(!(matrix && nc > SPG_WIDE_MATRIX_MAX_NC), "matrix filters at this width");
   SpgEdgeWgrad p;
   p.g = g; p.matrix = matrix; p.states = states; p.lds = lds; p.G = G; p.ldg = ldg; p.R = R; p.dW = dW;
-  const dim3 grid(spg_cdiv(g.E, 4)), block(SPG_THREADS);
   switch (nc) {
-    case 8: hipLaunchKernelGGL(spg_ecc_wide_edge_wgrad_kernel<8>, grid, block, 0, stream, p); break;
-    case 16: hipLaunchKernelGGL(spg_ecc_wide_edge_wgrad_kernel<16>, grid, block, 0, stream, p); break;
-    case 64: hipLaunchKernelGGL(spg_ecc_wide_edge_wgrad_kernel<64>, grid, block, 0, stream, p); break;
-    case 128: hipLaunchKernelGGL(spg_ecc_wide_edge_wgrad_kernel<128>, grid, block, 0, stream, p); break;
-    default: SPG_CHECK_ARG(false, "wide edge gradient: nc must be 8, 16, 64 or 128");
+    case 8: return launch_edge_wgrad<8>(p, stream);
+    case 16: return launch_edge_wgrad<16>(p, stream);
+    case 32: return spg_launch_ecc_edge_wgrad(g, matrix, states, lds, G, ldg, R, dW, stream);      // may join an open grouped launch
+    case 64: return launch_edge_wgrad<64>(p, stream);
+    case 128: return launch_edge_wgrad<128>(p, stream);
+    default: SPG_CHECK_ARG(false, "edge gradient: nc must be 8, 16, 32, 64 or 128");
   }
-  SPG_LAUNCH_CHECK();
   return 0;
 }

@@ -235,7 +235,7 @@ static int eccrnn_recurrent_forward(Plan& pl, const void* graph_ws, const float*
     p.agg_save = pl.training ? pl.agg + (size_t)r * nc : nullptr; p.ldagg = pl.ldS;
     p.do_gru = 1; p.gru = pl.gru; p.cell = pl.cfg.cell;
     if (pl.lstm) { p.cin = r > 0 ? pl.cells + (size_t)r * nc : nullptr; p.cout = pl.cells + (size_t)(r + 1) * nc; }
-    SPG_TRY(nc == 32 ? spg_launch_ecc_step_fwd(p, st) : spg_launch_ecc_step_fwd_wide(p, nc, st));
+    SPG_TRY(spg_ecc_step_fwd(p, nc, st));
   }
   if (pl.cfg.cat_all) SPG_TRY(spg_launch_copy2d(pl.states, pl.ldS, out, pl.ldS, N, (int)pl.ldS, st));
   else SPG_TRY(spg_launch_copy2d(pl.states + (size_t)pl.R * nc, pl.ldS, out, nc, N, nc, st));
@@ -361,8 +361,8 @@ void eccrnn_backward_tail_stages(std::shared_ptr<BwdCtx> c, std::vector<SpgStage
       return 0;
     }
     // per-edge filter gradients (sum over the iterations): the head of the filter network's chain
-    if (pl.nc == 32) SPG_TRY(spg_launch_ecc_edge_wgrad(c->gr, pl.cfg.matrix, pl.states, ldS, s.G, ldS, R, s.dWts, st));
-    else SPG_TRY(spg_launch_ecc_edge_wgrad_wide(c->gr, pl.cfg.matrix, pl.nc, pl.states, ldS, s.G, ldS, R, s.dWts, st));      // (its own launch, in stream order)
+    // (32: a job of the open grouped launch; the other widths: their own launch, in stream order)
+    SPG_TRY(spg_ecc_edge_wgrad(c->gr, pl.cfg.matrix, pl.nc, pl.states, ldS, s.G, ldS, R, s.dWts, st));
     c->cur = spg_op_ident(s.dWts, pl.nout);
     return 0;
   });
@@ -463,7 +463,7 @@ int spg_eccrnn_backward_phase(const spg_eccrnn_cfg* cfg, int N, int E, const voi
     p.dpre = s.dpre + (size_t)r * nc; p.xg = s.xg + (size_t)r * nc; p.ld32 = ldS;
     p.gru = pl.gru; p.cell = pl.cfg.cell;
     if (pl.lstm) { p.cin = r > 0 ? pl.cells + (size_t)r * nc : nullptr; p.dcdir = s.dcdir; p.use_dcdir = r < R - 1; }
-    SPG_TRY(nc == 32 ? spg_launch_ecc_step_bwd(p, st) : spg_launch_ecc_step_bwd_wide(p, nc, st));
+    SPG_TRY(spg_ecc_step_bwd(p, nc, st));
   }
   if (!persistent) {
     SpgEccStepBwd p; memset(&p, 0, sizeof(p));
@@ -471,7 +471,7 @@ int spg_eccrnn_backward_phase(const spg_eccrnn_cfg* cfg, int N, int E, const voi
     if (pl.cfg.cat_all) { p.dcat = grad_out; p.ldc = ldS; }
     p.Gnext = s.G; p.ldg = ldS; p.dhdir = s.dhdir; p.use_dhdir = 1; p.gx = grad_h0; p.final_only = 1;
     p.gru = pl.gru; p.cell = pl.cfg.cell;
-    SPG_TRY(nc == 32 ? spg_launch_ecc_step_bwd(p, st) : spg_launch_ecc_step_bwd_wide(p, nc, st));
+    SPG_TRY(spg_ecc_step_bwd(p, nc, st));
   }
   if (sc != nullptr && !persistent)       // per-iteration launches wrote grad_h0 [N, nc]: gather the embeddable rows
     SPG_TRY(spg_gather_rows(grad_h0, nc, sc->idx_valid, sc->B, nc, sc->grad_emb, nc, stream));

@@ -61,18 +61,13 @@ class _GRUCellFunction(torch.autograd.Function):
     def forward(ctx, cell, input, hidden, *params):
         ctx.cell = cell
         ctx.save_for_backward(input, hidden)
-        if cell.hidden_size != 32:
-            return ops.model.cell_fwd('gru', input, hidden, None, cell.param_tensors(), cell._layernorm, cell._ingate)[0]
         return ops.gru_cell_fwd(input, hidden, cell.param_tensors(), cell._layernorm, cell._ingate)
 
     @staticmethod
     def backward(ctx, grad_out):
         input, hidden = ctx.saved_tensors
         cell = ctx.cell
-        if cell.hidden_size != 32:
-            gi, gh, _, grads = ops.model.cell_bwd('gru', input, hidden, None, grad_out, None, cell.param_tensors(), cell._layernorm, cell._ingate)
-        else:
-            gi, gh, grads = ops.gru_cell_bwd(input, hidden, grad_out, cell.param_tensors(), cell._layernorm, cell._ingate)
+        gi, gh, grads = ops.gru_cell_bwd(input, hidden, grad_out, cell.param_tensors(), cell._layernorm, cell._ingate)
         return (None, gi, gh) + tuple(g for g in grads if g is not None)
 
 
@@ -91,16 +86,13 @@ class _LSTMCellFunction(torch.autograd.Function):
     def forward(ctx, cell, input, h, c, *params):
         ctx.cell = cell
         ctx.save_for_backward(input, h, c)
-        if cell.hidden_size != 32:
-            return ops.model.cell_fwd('lstm', input, h, c, cell.param_tensors(), cell._layernorm, cell._ingate)
         return ops.lstm_cell_fwd(input, h, c, cell.param_tensors(), cell._layernorm, cell._ingate)
 
     @staticmethod
     def backward(ctx, grad_hy, grad_cy):
         input, h, c = ctx.saved_tensors
         cell = ctx.cell
-        bwd = ops.lstm_cell_bwd if cell.hidden_size == 32 else (lambda *a: ops.model.cell_bwd('lstm', *a))
-        gi, gh, gc, grads = bwd(input, h, c, grad_hy, grad_cy, cell.param_tensors(), cell._layernorm, cell._ingate)
+        gi, gh, gc, grads = ops.lstm_cell_bwd(input, h, c, grad_hy, grad_cy, cell.param_tensors(), cell._layernorm, cell._ingate)
         return (None, gi, gh, gc) + tuple(g for g in grads if g is not None)
 
 

@@ -86,53 +86,7 @@ def ecc_aggregate_bwd(x, w, grad_out, graph: DeviceGraph, idxe=None, need_x=True
 
 
 # --------------------------------------------------------------------------------------------------
-# GRU cell
-# --------------------------------------------------------------------------------------------------
-def gru_cell_fwd(inp, hidden, params: Sequence[Optional[torch.Tensor]], layernorm: bool, ingate: bool):
-    _req(inp, torch.float32, 'input'); _req(hidden, torch.float32, 'hidden')
-    n = inp.shape[0]
-    out = torch.empty_like(hidden)
-    scratch = torch.empty(lib().spg_gru_scratch_floats(n), dtype=torch.float32, device=inp.device)
-    check(lib().spg_gru_cell_fwd(_ptr(inp), _ptr(hidden), n, _ptr_array(params), int(layernorm), int(ingate), _ptr(out),
-                                 _ptr(scratch), _stream()), 'spg_gru_cell_fwd')
-    return out
-
-
-def gru_cell_bwd(inp, hidden, grad_out, params, layernorm: bool, ingate: bool):
-    n = inp.shape[0]
-    grad_out = grad_out.contiguous()
-    gi, gh = torch.empty_like(inp), torch.empty_like(hidden)
-    grads = [None if p is None else torch.empty_like(p) for p in params]
-    scratch = torch.empty(lib().spg_gru_scratch_floats(n), dtype=torch.float32, device=inp.device)
-    check(lib().spg_gru_cell_bwd(_ptr(inp), _ptr(hidden), _ptr(grad_out), n, _ptr_array(params), int(layernorm), int(ingate),
-                                 _ptr(gi), _ptr(gh), _ptr_array(grads), _ptr(scratch), _stream()), 'spg_gru_cell_bwd')
-    return gi, gh, grads
-
-
-def lstm_cell_fwd(inp, h, c, params: Sequence[Optional[torch.Tensor]], layernorm: bool, ingate: bool):
-    _req(inp, torch.float32, 'input'); _req(h, torch.float32, 'hidden[0]'); _req(c, torch.float32, 'hidden[1]')
-    n = inp.shape[0]
-    hy, cy = torch.empty_like(h), torch.empty_like(c)
-    check(lib().spg_lstm_cell_fwd(_ptr(inp), _ptr(h), _ptr(c), n, _ptr_array(params), int(layernorm), int(ingate), _ptr(hy),
-                                  _ptr(cy), None, _stream()), 'spg_lstm_cell_fwd')
-    return hy, cy
-
-
-def lstm_cell_bwd(inp, h, c, grad_hy, grad_cy, params, layernorm: bool, ingate: bool):
-    n = inp.shape[0]
-    grad_hy = None if grad_hy is None else grad_hy.contiguous()
-    grad_cy = None if grad_cy is None else grad_cy.contiguous()
-    gi, gh, gc = torch.empty_like(inp), torch.empty_like(h), torch.empty_like(c)
-    grads = [None if p is None else torch.empty_like(p) for p in params]
-    scratch = torch.empty(lib().spg_lstm_scratch_floats(n), dtype=torch.float32, device=inp.device)
-    check(lib().spg_lstm_cell_bwd(_ptr(inp), _ptr(h), _ptr(c), _ptr(grad_hy), _ptr(grad_cy), n, _ptr_array(params),
-                                  int(layernorm), int(ingate), _ptr(gi), _ptr(gh), _ptr(gc), _ptr_array(grads), _ptr(scratch),
-                                  _stream()), 'spg_lstm_cell_bwd')
-    return gi, gh, gc, grads
-
-
-# --------------------------------------------------------------------------------------------------
-# GRU / LSTM cell at any supported width (spg_cell_fwd / spg_cell_bwd; 32 runs the kernels of the entries above)
+# GRU / LSTM cell at any supported width (spg_cell_fwd / spg_cell_bwd)
 # --------------------------------------------------------------------------------------------------
 CELL_KINDS = {'gru': 0, 'lstm': 1}
 CELL_WIDTHS = (8, 16, 32, 64, 128)            # state widths the HIP cells and the RNN-ECC recurrence serve
@@ -178,9 +132,8 @@ def cell_fwd(kind, inp, h, c, params: Sequence[Optional[torch.Tensor]], layernor
         _req(c, torch.float32, 'hidden[1]')
     hy = torch.empty_like(h)
     cy = torch.empty_like(h) if lstm else None
-    scratch = _cell_scratch(kind, nc, n, inp.device) if nc == 32 else None      # (the wide forward needs none; the 32-wide entries ask for theirs)
     _cell_check(lib().spg_cell_fwd(CELL_KINDS[kind], nc, _ptr(inp), _ptr(h), _ptr(c) if lstm else None, n, _ptr_array(params),
-                                   int(layernorm), int(ingate), _ptr(hy), _ptr(cy), _ptr(scratch), _stream()), 'spg_cell_fwd')
+                                   int(layernorm), int(ingate), _ptr(hy), _ptr(cy), None, _stream()), 'spg_cell_fwd')      # (no scratch)
     return hy, cy
 
 
@@ -199,6 +152,24 @@ def cell_bwd(kind, inp, h, c, grad_hy, grad_cy, params, layernorm: bool, ingate:
                                    _ptr_array(params), int(layernorm), int(ingate), _ptr(gi), _ptr(gh), _ptr(gc), _ptr_array(grads),
                                    _ptr(scratch), _stream()), 'spg_cell_bwd')
     return gi, gh, gc, grads
+
+
+# the per-kind names of the API: the same calls with `kind` fixed and the other cell's slots dropped
+def gru_cell_fwd(inp, hidden, params: Sequence[Optional[torch.Tensor]], layernorm: bool, ingate: bool):
+    return cell_fwd('gru', inp, hidden, None, params, layernorm, ingate)[0]
+
+
+def gru_cell_bwd(inp, hidden, grad_out, params, layernorm: bool, ingate: bool):
+    gi, gh, _, grads = cell_bwd('gru', inp, hidden, None, grad_out, None, params, layernorm, ingate)
+    return gi, gh, grads
+
+
+def lstm_cell_fwd(inp, h, c, params: Sequence[Optional[torch.Tensor]], layernorm: bool, ingate: bool):
+    return cell_fwd('lstm', inp, h, c, params, layernorm, ingate)
+
+
+def lstm_cell_bwd(inp, h, c, grad_hy, grad_cy, params, layernorm: bool, ingate: bool):
+    return cell_bwd('lstm', inp, h, c, grad_hy, grad_cy, params, layernorm, ingate)
 
 
 # --------------------------------------------------------------------------------------------------
