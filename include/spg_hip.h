@@ -236,7 +236,7 @@ int spg_eccrnn_forward(const spg_eccrnn_cfg* cfg, int N, int E, const void* grap
                        const float* edgefeats, const void* const* params, float* out, void* workspace, int training,
                        int bn_update_times, void* stream);
 /* test helper: byte offset inside the forward workspace of filter-network layer `layer`'s buffers (what: 0 raw output
- * [E, cout], 1 / 2 BatchNorm scale / shift of that layer); -1 if absent */
+ * [E, cout], 1 / 2 BatchNorm scale / shift of that layer, 3 / 4 its batch mean / 1 / sqrt(var + eps)); -1 if absent */
 long spg_eccrnn_debug_offset(const spg_eccrnn_cfg* cfg, int N, int E, int training, int layer, int what);
 size_t spg_eccrnn_bwd_workspace_bytes(const spg_eccrnn_cfg* cfg, int N, int E);
 int spg_eccrnn_backward(const spg_eccrnn_cfg* cfg, int N, int E, const void* graph_ws, const float* edgefeats,
@@ -593,7 +593,8 @@ int spg_prof_read_shapes(int* keys, double* vals, int max);
  * tests/test_gpu_precision.py); key 8: 1 = run the GRU recurrence of spg_eccrnn_forward / _backward as one launch per
  * iteration instead of the persistent dataflow-synchronised launch (A/B timing and the equality test; the two forms give
  * bit-identical results), 2 = only the iteration-major form for more nodes than wavefronts (round 5) is off.
- * key 10: 1 = train-mode BatchNorm statistics of spg_pointnet_forward go through per-workgroup partials and a finalize launch
+ * key 10: 1 = train-mode BatchNorm statistics of spg_pointnet_forward AND of the filter network of spg_eccrnn_forward /
+ * _backward (fnet_fold, csrc/spg_eccnet.hip) go through per-workgroup partials and a finalize launch
  * per layer (the pre-round-3 path, still used with synchronised BatchNorm) instead of fixed-point slots finished by the
  * consuming GEMM.  key 11: 1 = no grouped launches (round 4: mutually independent few-row GEMMs / small reductions leave as
  * jobs of ONE kernel; the bodies are unchanged, results bit-identical -- A/B timing and the equality test).

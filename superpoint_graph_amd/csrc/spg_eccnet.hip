@@ -286,7 +286,7 @@ extern "C" long spg_eccrnn_debug_offset(const spg_eccrnn_cfg* cfg, int N, int E,
   char* fake = (char*)(uintptr_t)4096;
   if (make_plan(cfg, N, E, training, fake, nullptr, pl) != 0 || layer < 0 || layer >= (int)pl.F.size()) return -1;
   const SpgDenseLayer& l = pl.F[layer];
-  const void* p = what == 0 ? (const void*)l.y : what == 1 ? l.s : l.t;
+  const void* p = what == 0 ? (const void*)l.y : what == 1 ? l.s : what == 2 ? l.t : what == 3 ? l.mean : what == 4 ? l.rstd : nullptr;
   return p == nullptr ? -1 : (long)((const char*)p - fake);
 }
 

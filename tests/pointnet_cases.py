@@ -601,6 +601,59 @@ def layer_input(case, state, clouds, glob, fw, l):
     return torch.relu(rec['y'].double() * rec['s'].double() + rec['t'].double())
 
 
+def check_raw(tag, ident, a, W, b, y, report=None):
+    """One layer's raw output y against a @ W^T + b in float64 (a: the layer's input as the run consumed it, float64; b may be None):
+    the derived dot-product bound of the module docstring, then conftest.assert_elementwise's defaults."""
+    W = W.double()
+    b = torch.zeros(W.shape[0], dtype=torch.float64) if b is None else b.double()
+    K = W.shape[1]
+    assert a.shape[1] == K and y.shape == (a.shape[0], W.shape[0]), (tag, a.shape, y.shape)
+    ref = a @ W.t() + b
+    bound = 2 * (K + 4) * U24 * (a.abs() @ W.abs().t() + b.abs())
+    err = (y.double() - ref).abs()
+    ratio = _worst(err, bound)
+    cpu = _worst(((a.float() @ W.float().t() + b.float()).double() - ref).abs(), bound)
+    print(f'{tag}: raw: worst error {float(err.max()) if err.numel() else 0.0:.3e}, {ratio:.3f} of the bound (float32 CPU {cpu:.3f})')
+    if report is not None:
+        report.append((ident, 'y', float(err.max()) if err.numel() else 0.0, ratio, cpu))
+    assert bool(torch.isfinite(y).all()) and ratio <= 1.0, f'{tag}: raw: worst element at {ratio:.3f} of the dot-product bound'
+    assert_elementwise(y, ref, what=f'{tag}: raw')
+
+
+def check_bn(tag, ident, y, gamma, beta, rm0, rv0, update_times, rec, got_running, report=None):
+    """The BatchNorm constants a run derived from its OWN raw output y [rows, C] (rec: mean, rstd, s, t) and the running statistics it
+    left (got_running: (running_mean, running_var); rm0 / rv0: before the forward) against the float64 statistics of y over exactly
+    its rows, with the bounds of the module docstring."""
+    y = y.double()
+    n = y.shape[0]
+    gamma, beta = gamma.double(), beta.double()
+    mean, ey2 = y.mean(0), (y * y).mean(0)
+    var = ((y - mean) ** 2).mean(0)
+    rms, rstd = ey2.sqrt(), 1.0 / torch.sqrt(var + EPS)
+    kappa = torch.sqrt(ey2 / (var + EPS)).clamp_min(1.0)
+    s64, t64 = gamma * rstd, beta - mean * gamma * rstd
+    b_mean, b_rstd = 1e-6 * rms, 1e-6 * kappa
+    b_s = gamma.abs() * rstd * b_rstd + U24 * s64.abs()
+    b_t = s64.abs() * b_mean + mean.abs() * gamma.abs() * rstd * b_rstd + U24 * t64.abs()
+    uvar = var * (n / max(n - 1, 1))
+    rm0, rv0 = rm0.double(), rv0.double()
+    rm, rv, keep = rm0, rv0, 1.0
+    for _ in range(update_times):
+        rm, rv, keep = (1 - MOMENTUM) * rm + MOMENTUM * mean, (1 - MOMENTUM) * rv + MOMENTUM * uvar, keep * (1 - MOMENTUM)
+    b_rm = 1e-6 * (keep * rm0.abs() + (1 - keep) * rms)
+    b_rv = 1e-6 * kappa * rv
+    got_rm, got_rv = got_running
+    for what, got, want, bnd in (('bn.mean', rec['mean'], mean, b_mean), ('bn.rstd', rec['rstd'].double() / rstd - 1, torch.zeros_like(rstd), b_rstd),
+                                 ('bn.s', rec['s'], s64, b_s), ('bn.t', rec['t'], t64, b_t),
+                                 ('running_mean', got_rm, rm, b_rm), ('running_var', got_rv, rv, b_rv)):
+        e = (got.double() - want).abs()
+        r = _worst(e, bnd)
+        print(f'{tag}: {what}: worst error {float(e.max()):.3e}, {r:.3f} of the bound')
+        if report is not None:
+            report.append((ident, what, float(e.max()), r, float('nan')))
+        assert bool(torch.isfinite(got).all()) and r <= 1.0, f'{tag}: {what}: worst channel at {r:.3f} of the bound'
+
+
 def check_forward(case, state, clouds, glob, fw, report=None):
     """Item 1 of the suite on one training run.  state: the parameters and the running statistics BEFORE the forward.
     report: list receiving (layer, tensor, worst error, error / bound, float32 CPU error / bound)."""
@@ -609,48 +662,11 @@ def check_forward(case, state, clouds, glob, fw, report=None):
         rec = fw['layers'][l['i']]
         tag = f"{name}: layer {l['i']} ({l['w']})"
         a = layer_input(case, state, clouds, glob, fw, l)
-        W, b = state[l['w'] + '.weight'].double(), state[l['w'] + '.bias'].double()
         assert a.shape[1] == l['cin'] and rec['y'].shape == (a.shape[0], l['cout']), (tag, a.shape, rec['y'].shape)
-        ref = a @ W.t() + b
-        bound = 2 * (l['cin'] + 4) * U24 * (a.abs() @ W.abs().t() + b.abs())
-        err = (rec['y'].double() - ref).abs()
-        ratio = _worst(err, bound)
-        cpu = _worst(((a.float() @ W.float().t() + b.float()).double() - ref).abs(), bound)
-        print(f'{tag}: raw: worst error {float(err.max()):.3e}, {ratio:.3f} of the bound (float32 CPU {cpu:.3f})')
-        if report is not None:
-            report.append((l['i'], 'y', float(err.max()), ratio, cpu))
-        assert bool(torch.isfinite(rec['y']).all()) and ratio <= 1.0, f'{tag}: raw: worst element at {ratio:.3f} of the dot-product bound'
-        assert_elementwise(rec['y'], ref, what=f'{tag}: raw')
-        if not l['bn']:
-            continue
-        y = rec['y'].double()
-        n = y.shape[0]
-        gamma, beta = state[l['n'] + '.weight'].double(), state[l['n'] + '.bias'].double()
-        mean, ey2 = y.mean(0), (y * y).mean(0)
-        var = ((y - mean) ** 2).mean(0)
-        rms, rstd = ey2.sqrt(), 1.0 / torch.sqrt(var + EPS)
-        kappa = torch.sqrt(ey2 / (var + EPS)).clamp_min(1.0)
-        s64, t64 = gamma * rstd, beta - mean * gamma * rstd
-        b_mean, b_rstd = 1e-6 * rms, 1e-6 * kappa
-        b_s = gamma.abs() * rstd * b_rstd + U24 * s64.abs()
-        b_t = s64.abs() * b_mean + mean.abs() * gamma.abs() * rstd * b_rstd + U24 * t64.abs()
-        uvar = var * (n / max(n - 1, 1))
-        rm0, rv0 = state[l['n'] + '.running_mean'].double(), state[l['n'] + '.running_var'].double()
-        rm, rv, keep = rm0, rv0, 1.0
-        for _ in range(case['update_times']):
-            rm, rv, keep = (1 - MOMENTUM) * rm + MOMENTUM * mean, (1 - MOMENTUM) * rv + MOMENTUM * uvar, keep * (1 - MOMENTUM)
-        b_rm = 1e-6 * (keep * rm0.abs() + (1 - keep) * rms)
-        b_rv = 1e-6 * kappa * rv
-        got_rm, got_rv = fw['running'][l['n']]
-        for what, got, want, bnd in (('bn.mean', rec['mean'], mean, b_mean), ('bn.rstd', rec['rstd'].double() / rstd - 1, torch.zeros_like(rstd), b_rstd),
-                                     ('bn.s', rec['s'], s64, b_s), ('bn.t', rec['t'], t64, b_t),
-                                     ('running_mean', got_rm, rm, b_rm), ('running_var', got_rv, rv, b_rv)):
-            e = (got.double() - want).abs()
-            r = _worst(e, bnd)
-            print(f'{tag}: {what}: worst error {float(e.max()):.3e}, {r:.3f} of the bound')
-            if report is not None:
-                report.append((l['i'], what, float(e.max()), r, float('nan')))
-            assert bool(torch.isfinite(got).all()) and r <= 1.0, f'{tag}: {what}: worst channel at {r:.3f} of the bound'
+        check_raw(tag, l['i'], a, state[l['w'] + '.weight'], state[l['w'] + '.bias'], rec['y'], report)
+        if l['bn']:
+            check_bn(tag, l['i'], rec['y'], state[l['n'] + '.weight'], state[l['n'] + '.bias'], state[l['n'] + '.running_mean'],
+                     state[l['n'] + '.running_var'], case['update_times'], rec, fw['running'][l['n']], report)
     for seg in ('stn', 'main'):
         if seg == 'stn' and not has_stn(case):
             continue
@@ -672,6 +688,21 @@ def check_forward(case, state, clouds, glob, fw, report=None):
     assert torch.equal(fw['emb'].view(torch.int32), fw['layers'][-1]['y'].view(torch.int32)), f'{name}: emb: not the last layer\'s output'
 
 
+def constant_ratio(tag, y_col, bias, beta, mean, rstd, s, t):
+    """A channel whose raw output is the constant `bias` on every row (asserted, with the batch mean within 1e-6 of it): the distance of
+    the normalised value y s + t from beta, in units of rstd ulp(y).  All arguments are the channel's scalars but y_col [rows]."""
+    assert bool((y_col == bias).all()), f'{tag}: constant: y is not the bias'
+    v = y_col.double() * s.double() + t.double()
+    ulp = float(torch.nextafter(bias.abs(), torch.tensor(float('inf'))) - bias.abs())
+    allowed = float(rstd) * ulp
+    off = float((v - beta.double()).abs().max())
+    dmean = abs(float(mean) - float(bias))
+    assert dmean <= 1e-6 * abs(float(bias)), f'{tag}: constant: bn.mean {dmean:.3e} from the constant'
+    print(f'{tag}: constant: mean {float(mean):.9g} (bias {float(bias):.9g}), normalised value {off:.3e} from beta, '
+          f'{off / allowed:.3f} of rstd ulp(y) = {allowed:.3e}')
+    return off / allowed
+
+
 def constant_channel(case, state, fw):
     """Edge c, an all-zero weight row (gamma = 1): y is the bias on every row (asserted), var = 0, and the normalised value y s + t
     should be beta within rstd ulp(y).  -> {layer prefix: distance from beta / (rstd ulp(y))}"""
@@ -679,17 +710,8 @@ def constant_channel(case, state, fw):
     for l in layers_of(case):
         if l['w'] in (EDGE_C_CONV, EDGE_C_FC):
             rec, c = fw['layers'][l['i']], EDGE_C_CH
-            bias = state[l['w'] + '.bias'][c]
-            assert bool((rec['y'][:, c] == bias).all()), f"{case['name']}: {l['w']}: constant: y is not the bias"
-            v = rec['y'][:, c].double() * rec['s'][c].double() + rec['t'][c].double()
-            ulp = float(torch.nextafter(bias.abs(), torch.tensor(float('inf'))) - bias.abs())
-            allowed = float(rec['rstd'][c]) * ulp
-            off = float((v - state[l['n'] + '.bias'][c].double()).abs().max())
-            dmean = abs(float(rec['mean'][c]) - float(bias))
-            assert dmean <= 1e-6 * abs(float(bias)), f"{case['name']}: {l['w']}: constant: bn.mean {dmean:.3e} from the constant"
-            print(f"{case['name']}: {l['w']}: constant: mean {float(rec['mean'][c]):.9g} (bias {float(bias):.9g}), normalised value {off:.3e} from beta, "
-                  f"{off / allowed:.3f} of rstd ulp(y) = {allowed:.3e}")
-            out[l['w']] = off / allowed
+            out[l['w']] = constant_ratio(f"{case['name']}: {l['w']}", rec['y'][:, c], state[l['w'] + '.bias'][c], state[l['n'] + '.bias'][c],
+                                         rec['mean'][c], rec['rstd'][c], rec['s'][c], rec['t'][c])
     return out
 
 
