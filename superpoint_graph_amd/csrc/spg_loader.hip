@@ -264,7 +264,7 @@ __global__ void spg_eval_accumulate_kernel(const float* __restrict__ logits, int
     // np.mean(np.stack(o, 0), 0): float32 sum over the samples in order, then one division (main.py:296-297)
     for (int s = 1; s < S; ++s) v += logits[s * sstride + (long)i * C + c];
     if (S > 1) v = v / (float)S;
-    if (c == 0 || v > bv) { bv = v; best = c; }      // np.argmax: the first maximum
+    if (c == 0 || v > bv || (v != v && bv == bv)) { bv = v; best = c; }      // np.argmax: the first maximum, a NaN counts as one
   }
   pred[i] = best;
   const int64_t t = label_mode[i];
@@ -281,9 +281,10 @@ __global__ void spg_eval_accumulate_kernel(const float* __restrict__ logits, int
 extern "C" int spg_eval_accumulate(const float* logits, int n_samples, long sample_stride, int N, int C,
                                    const int64_t* label_mode, const int64_t* label_vec, int64_t* pred,
                                    int64_t* confusion, int64_t* counters, void* stream) {
-  SPG_CHECK_ARG(logits && label_mode && label_vec && pred && confusion && counters, "null pointer");
   SPG_CHECK_ARG(n_samples >= 1 && N >= 0 && C >= 1, "n_samples >= 1, C >= 1");
-  if (N == 0) return 0;
+  SPG_CHECK_ARG(confusion && counters, "null pointer");
+  if (N == 0) return 0;                               // nothing to count: the per-row arrays are empty (and may be null)
+  SPG_CHECK_ARG(logits && label_mode && label_vec && pred, "null pointer");
   hipLaunchKernelGGL(spg_eval_accumulate_kernel, dim3(spg_cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, logits, n_samples,
                      sample_stride, N, C, label_mode, label_vec, pred, reinterpret_cast<unsigned long long*>(confusion),
                      reinterpret_cast<unsigned long long*>(counters));

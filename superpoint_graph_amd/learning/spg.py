@@ -353,7 +353,8 @@ def spg_edge_features_device(edges, node_att, edge_att, args, scaler=None, devic
     """`spg_edge_features` (+ the `scaler01` transform when a fitted sklearn StandardScaler is given) on the GPU: one
     thread per (edge, feature); float32 node attributes are combined in float32 and the u64 point count in float64 with
     one final rounding, exactly like the numpy expressions of the reference (learning/spg.py:23-64).  Copies, differences
-    and ratios are bit-identical to the host function; the logarithms are the device's logf / log."""
+    and ratios are bit-identical to the host function; the logarithms are the device's float64 log (for float32
+    attributes rounded once to float32, then subtracted in float32)."""
     from .. import ops
     dev = torch.device('cuda', torch.cuda.current_device()) if device is None else device
 

@@ -124,6 +124,8 @@ def load_superpoints(points, offsets, slot, sample_idx, colmap, xyznormalize: bo
         _req(noise, torch.float32, 'noise')
     clouds = torch.empty(n_valid, F, npts, dtype=torch.float32, device=points.device)
     diam = torch.empty(n_valid, dtype=torch.float32, device=points.device)
+    if n_valid == 0:      # no superpoint of ptn_minpts points (every slot -1): empty clouds, nothing to launch
+        return clouds, diam
     check(lib().spg_load_superpoints(_ptr(points), points.shape[1], _ptr(offsets), S, _ptr(slot), _ptr(sample_idx), npts,
                                      int(bool(xyznormalize)), ctypes.cast(colmap_h, ctypes.c_void_p), F, _ptr(M), _ptr(noise), _ptr(clouds),
                                      _ptr(diam), _stream()), 'spg_load_superpoints')
