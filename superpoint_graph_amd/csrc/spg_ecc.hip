@@ -341,6 +341,19 @@ __device__ __forceinline__ void spg_gru_lds_rows(const float* __restrict__ sw, i
   w.ig = sw + (2 * GW + (lane & 31)) * SPG_WLD;
 }
 
+// The five bias values a lane adds in the GRU's gates, held in REGISTERS by the one-launch recurrences (loaded once in front of
+// the group loop): fetched per iteration they are two dependent cache round trips between "aggregate ready" and "granule
+// stored" -- the part of an iteration every neighbour waits for.  The same values enter the same expressions: bit-identical.
+// The per-iteration kernels pass none (nullptr) and read the parameter arrays as before.
+struct GruLaneBias {
+  float ig, ih1, hh1, ih2, hh2;     // b_ig[lane & 31], b_ih[lane], b_hh[lane], b_ih[64 + (lane & 31)], b_hh[64 + (lane & 31)]
+  __device__ __forceinline__ void load(const SpgGruParams& G, int lane) {
+    ig = G.ingate ? G.b_ig[lane & 31] : 0.f;
+    ih1 = G.b_ih[lane]; hh1 = G.b_hh[lane];
+    ih2 = G.b_ih[64 + (lane & 31)]; hh2 = G.b_hh[64 + (lane & 31)];
+  }
+};
+
 template <class Rows, bool WAVE = false>
 __device__ __forceinline__ void spg_gru_forward_node(const SpgGruParams& G, const Rows& w, const float* __restrict__ sa,
                                                      const float* __restrict__ sh, float* __restrict__ sx, int lane,
@@ -387,10 +400,10 @@ __device__ __forceinline__ void spg_gru_forward_node(const SpgGruParams& G, cons
 // (tests/test_gpu_ecc_persistent.py compares the two kernels).
 template <class Rows>
 __device__ __forceinline__ void spg_gru_hidden_part(const SpgGruParams& G, const Rows& w, const float* __restrict__ sh, int lane,
-                                                    GruFwdState& st) {
+                                                    GruFwdState& st, const GruLaneBias* cb = nullptr) {
 #pragma clang fp contract(off)
   float gin = 1.f;
-  if (lane < 32 && G.ingate) gin = spg_sigmoid(w.dot_ig(sh) + G.b_ig[lane]);
+  if (lane < 32 && G.ingate) gin = spg_sigmoid(w.dot_ig(sh) + (cb != nullptr ? cb->ig : G.b_ig[lane]));
   st.gin = gin;
   float gh1 = w.dot_hh1(sh), gh2 = 0.f;
   if (lane < 32) gh2 = w.dot_hh2(sh);
@@ -407,7 +420,7 @@ __device__ __forceinline__ void spg_gru_hidden_part(const SpgGruParams& G, const
 
 template <class Rows, bool WAVE>
 __device__ __forceinline__ void spg_gru_input_part(const SpgGruParams& G, const Rows& w, const float* __restrict__ sa,
-                                                   float* __restrict__ sx, int lane, GruFwdState& st) {
+                                                   float* __restrict__ sx, int lane, GruFwdState& st, const GruLaneBias* cb = nullptr) {
 #pragma clang fp contract(off)
   float x = 0.f;
   if (lane < 32) {
@@ -428,22 +441,22 @@ __device__ __forceinline__ void spg_gru_input_part(const SpgGruParams& G, const 
   }
   st.ui1 = gi1; st.ui2 = gi2;
   const float gh1 = st.uh1, gh2 = st.uh2;
-  const float g1 = spg_sigmoid(((gi1 + G.b_ih[lane]) + gh1) + G.b_hh[lane]);
+  const float g1 = spg_sigmoid(((gi1 + (cb != nullptr ? cb->ih1 : G.b_ih[lane])) + gh1) + (cb != nullptr ? cb->hh1 : G.b_hh[lane]));
   st.r = g1;
   st.z = __shfl(g1, (lane & 31) + 32, 64);
   st.n = 0.f;
-  if (lane < 32) st.n = tanhf((gi2 + G.b_ih[64 + lane]) + g1 * (gh2 + G.b_hh[64 + lane]));
+  if (lane < 32) st.n = tanhf((gi2 + (cb != nullptr ? cb->ih2 : G.b_ih[64 + lane])) + g1 * (gh2 + (cb != nullptr ? cb->hh2 : G.b_hh[64 + lane])));
 }
 
 // forward internals of one (node, iteration) kept for the backward (persistent kernels, training): SPG_PX_SAVE_F values per lane
 #define SPG_PX_SAVE_MAGIC 0x53504721u
-// three 16-byte stores / loads per lane (1 KiB per wave instruction): `s` points at this lane's first quad, quads 64 apart
+// three 16-byte stores / loads per lane (1 KiB per wave instruction): `s` points at this lane's first quad, quads 64 apart (the
+// backward loads the quads itself, with everything else an iteration reads, and unpacks them behind its gather)
 __device__ __forceinline__ void spg_px_save_state(f32x4* __restrict__ s, const GruFwdState& st) {
   const f32x4 a = {st.gin, st.x, st.ui1, st.ui2}, b = {st.uh1, st.uh2, st.rstd_i, st.rstd_h}, c = {st.r, st.z, st.n, 0.f};
   s[0] = a; s[64] = b; s[128] = c;
 }
-__device__ __forceinline__ void spg_px_load_state(const f32x4* __restrict__ s, GruFwdState& st) {
-  const f32x4 a = s[0], b = s[64], c = s[128];
+__device__ __forceinline__ void spg_px_unpack_state(const f32x4& a, const f32x4& b, const f32x4& c, GruFwdState& st) {
   st.gin = a[0]; st.x = a[1]; st.ui1 = a[2]; st.ui2 = a[3];
   st.uh1 = b[0]; st.uh2 = b[1]; st.rstd_i = b[2]; st.rstd_h = b[3];
   st.r = c[0]; st.z = c[1]; st.n = c[2];
@@ -577,14 +590,15 @@ template <bool WAVE, int UNR = 8>
 __device__ __forceinline__ void spg_gru_backward_node(const SpgGruParams& G, const float* __restrict__ sw, float* sa, float* sh,
                                                       float* sx, float* sd, int lane, bool active, long j, float dH,
                                                       const SpgGruBwdOut& o, float& dh_acc, float& da,
-                                                      const GruFwdState* saved = nullptr) {
+                                                      const GruFwdState* saved = nullptr, bool use_saved = true,
+                                                      const GruLaneBias* cb = nullptr) {
   constexpr int GW = 96;
   const float* sw_ih = sw;
   const float* sw_hh = sw_ih + GW * SPG_WLD;
   const float* sw_ig = sw_hh + GW * SPG_WLD;
   {
     GruFwdState st;
-    if (saved != nullptr) {      // the forward kernel kept its internals (persistent kernels): nothing to recompute
+    if (saved != nullptr && use_saved) {      // the forward kernel kept its internals (persistent kernels): nothing to recompute
       st = *saved;
     } else {
       GruRowsLds wr;
@@ -601,7 +615,7 @@ __device__ __forceinline__ void spg_gru_backward_node(const SpgGruParams& G, con
       const float dzg = dH * (h_in - st.n);
       dh_acc = dH * st.z;
       dn_pre = dn * (1.f - st.n * st.n);
-      const float dr = dn_pre * (st.uh2 + G.b_hh[64 + lane]);
+      const float dr = dn_pre * (st.uh2 + (cb != nullptr ? cb->hh2 : G.b_hh[64 + lane]));
       dz_pre = dzg * st.z * (1.f - st.z);
       dr_pre = dr * st.r * (1.f - st.r);
     }
@@ -1309,10 +1323,21 @@ extern "C" int spg_ecc_phase_times(unsigned long long* out, int clear) {
 #define SPG_XP(k) { const unsigned long long n__ = __builtin_readcyclecounter(); xp__[k] += n__ - xt__; xt__ = n__; }
 #define SPG_XEND() if ((threadIdx.x & 63) == 0) { for (int k__ = 0; k__ < 6; ++k__) atomicAdd(&spg_ecc_phase_t[k__], xp__[k__]); \
     for (int k__ = 7; k__ < 11; ++k__) atomicAdd(&spg_ecc_phase_t[k__], xp__[k__]); if (xp__[4] != 0) atomicAdd(&spg_ecc_phase_t[6], 1ull); }
+// the same for the one-launch backward recurrence: [0 entry (edge ids, filter loads, slot R), 1 an iteration's loads, 2 waiting for +
+//  gathering the neighbours' gradients, 3 out-edge products, 4 cell backward, 5 publish, 6 waves]
+__device__ unsigned long long spg_ecc_bwd_phase_t[8];
+extern "C" int spg_ecc_bwd_phase_times(unsigned long long* out, int clear) {
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(spg_ecc_bwd_phase_t), sizeof(unsigned long long) * 8) != hipSuccess) return -1;
+  if (clear) { unsigned long long z[8] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(spg_ecc_bwd_phase_t), z, sizeof(z)) != hipSuccess) return -1; }
+  return 0;
+}
+#define SPG_XBEND() if ((threadIdx.x & 63) == 0) { for (int k__ = 0; k__ < 6; ++k__) atomicAdd(&spg_ecc_bwd_phase_t[k__], xp__[k__]); \
+    if (xp__[5] != 0) atomicAdd(&spg_ecc_bwd_phase_t[6], 1ull); }
 #else
 #define SPG_X0()
 #define SPG_XP(k)
 #define SPG_XEND()
+#define SPG_XBEND()
 #endif
 
 template <bool MATRIX, int KMAX, int WPC, bool GROUPS>
@@ -1337,6 +1362,11 @@ __global__ __launch_bounds__(256, WPC) void spg_ecc_persist_fwd_kernel(const Spg
     e0_early = p.g.rowptr[ic]; deg_early = p.g.rowptr[ic + 1] - e0_early;
     invdeg_early = p.g.invdeg[ic];
   }
+  // (in front of the weight staging: in-order counter, no wait of their own.  Two workgroups per CU: no registers to spare for
+  //  them -- the matrix build would spill -- so that build reads the parameter arrays per iteration as before)
+  GruLaneBias cbv;
+  if constexpr (WPC == 1) cbv.load(p.gru, lane0);
+  const GruLaneBias* cb = WPC == 1 ? &cbv : nullptr;
   SPG_XP(7);
   spg_stage_cell_weights<96>(p.gru, sw);
   SPG_XP(8);
@@ -1440,7 +1470,7 @@ __global__ __launch_bounds__(256, WPC) void spg_ecc_persist_fwd_kernel(const Spg
     if (lane < 32) sh[lane] = hcur;
     spg_node_sync<true>();
     GruFwdState st;
-    spg_gru_hidden_part(p.gru, wq, sh, lane, st);
+    spg_gru_hidden_part(p.gru, wq, sh, lane, st, cb);
     if (with_head && p.cat_all) spg_px_head_accum(swc, hd_ldw, 32 * r, sh, lane, p.head.C, hlog);      // the classifier's share of h^r
     // ---- aggregate over the in-edges: mean of h_src (.) W_e ----
     float a4[4] = {0.f, 0.f, 0.f, 0.f};
@@ -1508,7 +1538,7 @@ __global__ __launch_bounds__(256, WPC) void spg_ecc_persist_fwd_kernel(const Spg
     spg_node_sync<true>();
     SPG_XP(3);
     // ---- the input half of the GRU ----
-    spg_gru_input_part<Rows, true>(p.gru, wq, sa, sx, lane, st);
+    spg_gru_input_part<Rows, true>(p.gru, wq, sa, sx, lane, st, cb);
     if (lane < 32) {
       hcur = st.n + st.z * (hcur - st.n);      // hy = newgate + inputgate * (hidden - newgate), learning/modules.py:250
       // publish FIRST: the neighbours wait for this; everything the later kernels need follows behind it in the memory pipeline
@@ -1559,6 +1589,7 @@ __global__ __launch_bounds__(256, WPC) void spg_ecc_persist_bwd_kernel(const Spg
     spg_px_finish(p.ctl, base, (unsigned)p.R + 2u);
     return;
   }
+  SPG_X0();
   int b0_early = 0, odeg_early = 0;      // (see the forward kernel: the first link of row -> edge ids -> destinations -> filters)
   float invdeg_early = 0.f;
   if constexpr (!GROUPS) {
@@ -1567,6 +1598,8 @@ __global__ __launch_bounds__(256, WPC) void spg_ecc_persist_bwd_kernel(const Spg
     b0_early = p.g.rev_rowptr[jc]; odeg_early = p.g.rev_rowptr[jc + 1] - b0_early;
     invdeg_early = p.g.invdeg[jc];
   }
+  GruLaneBias cb;             // (the cell backward reads hh2 only)
+  cb.load(p.gru, lane0);
   spg_stage_cell_weights<GW>(p.gru, sw);
   const unsigned base = __hip_atomic_load((spg_gu32*)p.ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const unsigned spin_limit = spg_px_spin_limit(p.ctl);
@@ -1593,19 +1626,24 @@ __global__ __launch_bounds__(256, WPC) void spg_ecc_persist_bwd_kernel(const Spg
   spg_node_sync<true>();
   const int b0 = GROUPS ? p.g.rev_rowptr[j] : b0_early, odeg = GROUPS ? p.g.rev_rowptr[j + 1] - b0 : odeg_early;
   const float invdeg = GROUPS ? p.g.invdeg[j] : invdeg_early;
-  // out-edge list (edge id, destination) and the filters of the first KMAX out-edges: resident for all iterations
-  if (odeg <= SPG_PX_CH && lane < odeg) {
-    const int e = p.g.rev_eid[b0 + lane];
-    eis[lane] = e; ids[lane] = p.g.dst[e];
-  }
-  spg_node_sync<true>();
+  // out-edge list (edge id, destination) and the filters of the first KMAX out-edges: resident for all iterations.  The edge
+  // ids first -- lane u holds the id of out-edge u, the filter loop reads it from there as a scalar -- then ALL filter loads back
+  // to back, as the forward kernel issues its own (fetched one by one through the LDS list, every edge was a round trip of its own
+  // into an array no cache holds, up to KMAX of them in front of the node's first gather)
+  int e_l = 0;
+  if (lane < odeg && (odeg <= SPG_PX_CH || lane < KMAX)) e_l = p.g.rev_eid[b0 + lane];
+  int d_l = 0;
+  if (odeg <= SPG_PX_CH && lane < odeg) d_l = p.g.dst[e_l];
+  int ef[KMAX];
+#pragma unroll
+  for (int u = 0; u < KMAX; ++u) ef[u] = __builtin_amdgcn_readlane(e_l, u);
   f32x4 wc[MATRIX ? KMAX : 1][4];
   float wv[KMAX];
 #pragma unroll
   for (int u = 0; u < KMAX; ++u) {
     wv[u] = 0.f;
     if (u < odeg) {
-      const int e = odeg <= SPG_PX_CH ? eis[u] : p.g.rev_eid[b0 + u];
+      const int e = ef[u];
       if constexpr (MATRIX) {
         const f32x4* We = reinterpret_cast<const f32x4*>(p.W + (long)e * 1024);
 #pragma unroll
@@ -1613,6 +1651,17 @@ __global__ __launch_bounds__(256, WPC) void spg_ecc_persist_bwd_kernel(const Spg
       } else {
         wv[u] = p.W[(long)e * 32 + (lane & 31)];
       }
+    }
+  }
+  if (odeg <= SPG_PX_CH && lane < odeg) { eis[lane] = e_l; ids[lane] = d_l; }      // (read behind the iterations' own wave syncs)
+  // The out-edge products pair the filters' elements ACROSS the four quads of an edge (packed multiplies): left alone, the compiler
+  // rearranges every quad where it is loaded and waits for it there -- one round trip per edge again.  Behind this point the values
+  // are new to it: the loads above stay a plain batch, the rearranging follows here, once, when all of them have arrived.
+  if constexpr (MATRIX) {
+#pragma unroll
+    for (int u = 0; u < KMAX; ++u) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) asm volatile("" : "+v"(wc[u][q]));
     }
   }
   // slot R of the per-iteration gradient matrices has no producer, but the deferred weight-gradient GEMMs and column sums run
@@ -1630,27 +1679,34 @@ __global__ __launch_bounds__(256, WPC) void spg_ecc_persist_bwd_kernel(const Spg
   // did the forward keep its internals for this workspace?  (the per-iteration forward clears the tag)
   const bool saved = p.fsave != nullptr && p.fsave_tag != nullptr &&
                      __hip_atomic_load((const spg_gu32*)p.fsave_tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == SPG_PX_SAVE_MAGIC;
+  SPG_XP(0);
   // iterations R-1 .. 0 produce G^r; the extra pass r = -1 only forms the gradient wrt h^0
   for (int r = p.R - 1; r >= -1; --r) {
     // two workgroups per CU (256 registers per wave): the per-lane address arithmetic of an iteration must not be hoisted out of the
     // iteration loop either -- it would stay live across the whole body
     const int lane = laneg + (WPC == 2 ? spg_opaque_lane_zero() : 0);
-    GruFwdState stf;            // issued before the wait for the neighbours' gradients: the loads are in flight while the wave polls
-    if (saved && r >= 0) spg_px_load_state(reinterpret_cast<const f32x4*>(p.fsave) + ((long)j * p.R + r) * (SPG_PX_SAVE_F / 4) * 64 + lane, stf);
-    // the forward's aggregate and state of this iteration (phase 2 needs them) depend on nothing the wave waits for either: one L2
-    // round trip less between the neighbours' gradients and this node's granule (one workgroup per CU: the registers are there)
-    float a_pre = 0.f, h_pre = 0.f;
-    if (WPC == 1 && r >= 0 && lane < 32) {
-      a_pre = p.agg[(long)j * p.ldS + (long)r * 32 + lane];
-      h_pre = p.states[(long)j * p.ldS + (long)r * 32 + lane];
+    // Everything an iteration reads that depends on (j, r) only -- the forward's internals, its aggregate and state (phase 2 needs
+    // them; one workgroup per CU: the registers are there) and the output gradient's row -- is requested here as ONE batch and first
+    // used behind the gather: the loads are in flight while the wave polls.  No branch and no initialisation between them (a
+    // load under `r >= 0` next to a zero for the other case made the compiler wait for every load in turn: three round trips in a
+    // row in front of the first poll): the extra pass r = -1 reads the rows of iteration 0 and uses none of them, and lanes 32..63
+    // read the row of lanes 0..31.
+    const int rc = r < 0 ? 0 : r, l32 = lane & 31;
+    f32x4 fq0, fq1, fq2;
+    if (saved) {
+      const f32x4* fs = reinterpret_cast<const f32x4*>(p.fsave) + ((long)j * p.R + rc) * (SPG_PX_SAVE_F / 4) * 64 + lane;
+      fq0 = fs[0]; fq1 = fs[64]; fq2 = fs[128];
     }
+    float a_pre, h_pre;
+    if (WPC == 1) {
+      a_pre = p.agg[(long)j * p.ldS + (long)rc * 32 + l32];
+      h_pre = p.states[(long)j * p.ldS + (long)rc * 32 + l32];
+    }
+    float go = 0.f;             // (cat_all: slot r + 1 of the row; else the gradient wrt h^R, in the first pass only)
+    if (p.cat_all || r == p.R - 1) go = p.grad_out[(long)j * p.ldgo + (p.cat_all ? (long)(r + 1) * 32 : 0) + l32];
+    SPG_XP(1);
     // ---- phase 1: dH = d(out)/d(h^{r+1}) + dhdir + sum over the out-edges of W_e . G^{r+1}[dst] ----
-    float dH = 0.f;
-    if (lane < 32) {
-      if (p.cat_all) dH = p.grad_out[(long)j * p.ldgo + (long)(r + 1) * 32 + lane];
-      else if (r == p.R - 1) dH = p.grad_out[(long)j * p.ldgo + lane];
-      dH += dhdir;
-    }
+    float dH = 0.f, nb = 0.f;      // (nb: the neighbours' share)
     if (r < p.R - 1) {
       float pq[4] = {0.f, 0.f, 0.f, 0.f};
       float acc = 0.f;
@@ -1663,6 +1719,7 @@ __global__ __launch_bounds__(256, WPC) void spg_ecc_persist_bwd_kernel(const Spg
         spg_node_sync<true>();
         spg_px_gather_granules(gran + (long)(r + 1) * SPG_PX_MAX_NODES * 32, base + (unsigned)(r + 1) + 1u, ids, n, lane, hs, p.ctl, spin_limit);
         spg_node_sync<true>();
+        SPG_XP(2);
         if constexpr (MATRIX) {
           if (c0 == 0) {
 #pragma unroll
@@ -1705,16 +1762,23 @@ __global__ __launch_bounds__(256, WPC) void spg_ecc_persist_bwd_kernel(const Spg
           for (int q = 0; q < 4; ++q) sd[(lane >> 3) + 8 * q] = pq[q];   // input channel k = lane/8 + 8q
         }
         spg_node_sync<true>();
-        if (lane < 32) dH += sd[lane];
+        if (lane < 32) nb = sd[lane];
       } else {
-        dH += acc;
+        nb = acc;
       }
     }
+    if (lane < 32) {      // (the order of the sum as in the per-iteration kernel: (output gradient + direct path) + neighbours)
+      dH = go;
+      dH += dhdir;
+      if (r < p.R - 1) dH += nb;
+    }
+    SPG_XP(3);
     if (r < 0) {
       if (lane < 32) {
         const long grow = p.gx_rows != nullptr ? p.gx_rows[j] : (long)j;      // (< 0: a node without an embedding -- nobody reads its gradient)
         if (grow >= 0) p.gx[grow * 32 + lane] = dH;
       }
+      SPG_XP(5);
       break;
     }
     // ---- phase 2: GRU recompute + backward of iteration r ----
@@ -1727,16 +1791,21 @@ __global__ __launch_bounds__(256, WPC) void spg_ecc_persist_bwd_kernel(const Spg
     SpgGruBwdOut o;
     o.dgi = p.dgi + (long)r * GW; o.dgh = p.dgh + (long)r * GW; o.dui = p.dui + (long)r * GW; o.duh = p.duh + (long)r * GW;
     o.dpre = p.dpre + (long)r * 32; o.xg = p.xg + (long)r * 32; o.ld96 = p.ld96; o.ld32 = p.ld32;
+    GruFwdState stf;
+    if (saved) spg_px_unpack_state(fq0, fq1, fq2, stf);
     float dh_acc, da;
-    spg_gru_backward_node<true, (WPC == 1 ? 8 : 2)>(p.gru, sw, sa, sh, sx, sd, lane, true, j, dH, o, dh_acc, da, saved ? &stf : nullptr);
+    spg_gru_backward_node<true, (WPC == 1 ? 8 : 2)>(p.gru, sw, sa, sh, sx, sd, lane, true, j, dH, o, dh_acc, da, &stf, saved, &cb);
+    SPG_XP(4);
     if (lane < 32) {
       dhdir = dh_acc;
       const float gc = da * invdeg;
       spg_px_store_granule(gran + ((long)r * SPG_PX_MAX_NODES + j) * 32 + lane, base + (unsigned)r + 1u, gc);
       p.G[(long)j * p.ldS + (long)r * 32 + lane] = gc;
     }
+    SPG_XP(5);
   }
   }      // groups
+  SPG_XBEND();
   // the loss of the head the forward launch ran (SpgEccHead): nobody on the device waits for it
   if (p.head.W != nullptr && blockIdx.x == 0 && (int)gridDim.x == p.node_wgs) spg_px_head_loss(p.head, hd_part[0], hd_part[1], hd_flag);
   spg_px_finish(p.ctl, base, (unsigned)p.R + 2u);
@@ -1761,6 +1830,8 @@ __global__ __launch_bounds__(256, 3) void spg_ecc_persist_fwd_multi_kernel(const
   __shared__ int idb[4][SPG_PX_CH];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int S = (int)gridDim.x * 4, slot = (int)blockIdx.x * 4 + wave, N = p.g.N;
+  GruLaneBias cb;
+  cb.load(p.gru, lane);
   spg_stage_cell_weights<96>(p.gru, sw);
   const unsigned base = __hip_atomic_load((spg_gu32*)p.ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const unsigned spin_limit = spg_px_spin_limit(p.ctl);
@@ -1801,7 +1872,7 @@ __global__ __launch_bounds__(256, 3) void spg_ecc_persist_fwd_multi_kernel(const
       if (deg <= SPG_PX_CH && lane < deg) ids[lane] = p.g.src[e0 + lane];
       spg_node_sync<true>();
       GruFwdState st;
-      spg_gru_hidden_part(p.gru, wq, sh, lane, st);
+      spg_gru_hidden_part(p.gru, wq, sh, lane, st, &cb);
       // ---- aggregate over the in-edges: mean of h_src (.) W_e, filters through L2 ----
       float a4[4] = {0.f, 0.f, 0.f, 0.f};
       for (int c0 = 0; c0 < deg; c0 += SPG_PX_CH) {
@@ -1845,7 +1916,7 @@ __global__ __launch_bounds__(256, 3) void spg_ecc_persist_fwd_multi_kernel(const
         sa[lane] = a4[0] * invdeg;
       }
       spg_node_sync<true>();
-      spg_gru_input_part<GruRowsLds, true>(p.gru, wq, sa, sx, lane, st);
+      spg_gru_input_part<GruRowsLds, true>(p.gru, wq, sa, sx, lane, st, &cb);
       if (lane < 32) {
         hcur = st.n + st.z * (hcur - st.n);      // learning/modules.py:250
         if (r + 1 < p.R) spg_px_store_granule(p.gran + (long)(r + 1) * GS + (long)i * 32 + lane, base + (unsigned)r + 2u, hcur);

@@ -1,4 +1,4 @@
-"""Cycles per phase of the one-launch forward RNN-ECC recurrence (attribution build: tools/build_variant.sh attr "-DSPG_ATTRIBUTION" spg_gemm.hip spg_ecc.hip).
+"""Cycles per phase of the one-launch forward and backward RNN-ECC recurrences (attribution build: tools/build_variant.sh attr "-DSPG_ATTRIBUTION" spg_gemm.hip spg_ecc.hip).
    SPG_HIP_LIB=<variant .so> python tools/ecc_phase_timing.py"""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -30,6 +30,9 @@ def main():
     torch.cuda.synchronize()
     buf = (ctypes.c_ulonglong * 12)()
     h.spg_ecc_phase_times(buf, 1)
+    h.spg_ecc_bwd_phase_times.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_int]
+    bbuf = (ctypes.c_ulonglong * 8)()
+    h.spg_ecc_bwd_phase_times(bbuf, 1)
     n = 10
     for _ in range(n): run()
     torch.cuda.synchronize()
@@ -42,6 +45,14 @@ def main():
     for k in range(6):
         v = buf[k] / waves
         print(f'   {names[k]:45s} {v:8.0f} cycles ({100 * v / tot:4.1f} %)' + (f' = {v / 10:.0f} per iteration' if 1 <= k <= 4 else ''))
+    h.spg_ecc_bwd_phase_times(bbuf, 0)
+    waves = max(bbuf[6], 1)
+    names = ['entry: edge ids, filter loads, slot R', 'an iteration\'s loads (issue)', 'waiting for + gathering the neighbours', 'out-edge products + sum', 'cell backward', 'publish']
+    tot = sum(bbuf[k] for k in range(6)) / waves
+    print(f'backward recurrence, 10 iterations + the pass for h^0: {waves / n:.0f} node waves per launch, {tot:.0f} cycles per wave')
+    for k in range(6):
+        v = bbuf[k] / waves
+        print(f'   {names[k]:45s} {v:8.0f} cycles ({100 * v / tot:4.1f} %)' + (f' = {v / 10:.0f} per iteration' if k >= 1 else ''))
 
 
 if __name__ == '__main__':
