@@ -137,6 +137,12 @@ int spg_linear_backward(const float* dY, long lddy, const float* X, long ldx, co
  * (grads: {d weight, d bias, d bn.weight, d bn.bias, NULL, NULL}).  With nfeat_stn == 0 the STN
  * groups are omitted.
  * clouds [B, nfeat, npts] fp32, clouds_global [B, nfeat_global]; emb [B, fc[n_fc-1]].
+ * Supported npts: 1 ... 128 (a superpoint is one row tile), or 129 ... 4095 with a divisor in [32, 128]: the largest such divisor
+ * Ps is the segment length, and the convolutions run on B * npts / Ps segments of Ps points (256 = 2 x 128, 384 = 3 x 128,
+ * 160 = 2 x 80, 200 = 2 x 100, 1000 = 8 x 125; 131 and 262 have no such divisor).  The max-pool is merged over the segments of a
+ * superpoint (first extremum wins), the pooled rows, the winners (point index 0 ... npts - 1) and every result keep their
+ * [B, ...] shape.  Any other npts: the workspace queries return 0 and the entry points -2, spg_last_error() states the rule.
+ * nfeat <= 32.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct spg_pointnet_cfg {
   int nfeat, nfeat_stn, nfeat_global, npts;

@@ -13,10 +13,15 @@
 //   The max-pool over the points is fused into the epilogue of the last conv (per-superpoint max AND
 //   min of the raw output: after the batch statistics are known, sign(s) decides which one is the
 //   max of the normalised value -- BatchNorm is monotone per channel).
+//   More than 128 points per superpoint (spg_segments.h): the convolutions run on Bc = B * S pseudo-superpoints of Pc = P / S points
+//   in the same row space (row b*P + p = (b*S + s)*Pc + p'); the clouds and transforms are copied into that view, the epilogue's
+//   per-segment extrema are merged into pooled / aidx [B, ldpool] (winner = point index in the superpoint), and the backward expands
+//   the pooled gradient back to per-segment rows.  Up to 128 points S = 1 and nothing of this is launched or allocated.
 #include "../../include/spg_hip.h"
 #include "spg_ecc.h"
 #include "spg_dense.h"
 #include "spg_narrow.h"
+#include "spg_segments.h"
 #include <limits.h>
 #include <mutex>
 #include <unordered_map>
@@ -51,12 +56,20 @@ struct Segment {           // convs (BN+ReLU each) -> max-pool (+concat) -> fcs 
   int nextra = 0;
   const float* extra = nullptr;
   unsigned long long* gram = nullptr;   // train mode: fixed-point slots of the Gram matrix of the segment's input (spg_narrow.h)
+  // npts > 128 (spg_segments.h): what the pooled convolution writes per pseudo-superpoint, [Bc, ldseg]; pooled / aidx are merged from them
+  float* spool = nullptr;
+  int* sidx = nullptr;
+  long ldseg = 0;
 };
 
 struct Plan {
   spg_pointnet_cfg cfg;
   int B = 0, P = 0;
   long M = 0;
+  // the convolutions' view: Bc = B * S pseudo-superpoints of Pc points (spg_segments.h); S = 1, Bc = B, Pc = P up to 128 points
+  int S = 1, Bc = 0, Pc = 0;
+  float* seg_clouds = nullptr;   // S > 1: [Bc, nfeat, Pc] copy of the clouds
+  float* seg_T = nullptr;        // S > 1: [Bc, 4] rows of the transform (inner STN's projection or external)
   bool training = false;
   std::vector<Layer> L;
   Segment stn, main;
@@ -81,13 +94,19 @@ int make_plan(const spg_pointnet_cfg* cfg, int B, int training, void* ws, const 
               Plan& pl) {
   SPG_CHECK_ARG(cfg != nullptr && B > 0, "cfg / B");
   const spg_pointnet_cfg& c = *cfg;
-  SPG_CHECK_ARG(c.npts >= 1 && c.npts <= 128, "npts must be in [1,128]");
+  int Ps = 0, S = 0;
+  if (!spg_segment_plan(c.npts, &Ps, &S)) {
+    spg_set_error("PointNet: npts = %d is not supported: " SPG_SEG_RULE, c.npts);
+    return -2;
+  }
   SPG_CHECK_ARG(c.n_conv >= 1 && c.n_fc >= 1 && c.n_conv <= SPG_MAX_LAYERS && c.n_fc <= SPG_MAX_LAYERS, "layer counts");
   SPG_CHECK_ARG(c.last_ac == 0, "last_ac=True is not supported");
   SPG_CHECK_ARG(c.nfeat_stn == 0 || (c.nfeat_stn >= 2 && c.nfeat_stn <= c.nfeat && c.n_stn_conv >= 1 && c.n_stn_fc >= 1),
                 "STN configuration");
   SPG_CHECK_ARG(c.nfeat >= 1 && c.nfeat <= 32, "nfeat must be <= 32");
   pl.cfg = c; pl.B = B; pl.P = c.npts; pl.M = (long)B * c.npts; pl.training = training != 0;
+  pl.S = S; pl.Pc = Ps; pl.Bc = B * S;
+  SPG_CHECK_ARG((long)B * c.npts < (1L << 31), "B * npts");
   pl.has_stn = c.nfeat_stn > 0;
   pl.L.clear();
   auto add = [&](int cin, int cout, bool bn, bool conv) {
@@ -151,6 +170,11 @@ int make_plan(const spg_pointnet_cfg* cfg, int B, int training, void* ws, const 
     if (pl.has_stn) { pl.stn.gram = pl.slots_all ? pl.slots_all + off : nullptr; off += gw_stn; }
     pl.main.gram = pl.slots_all ? pl.slots_all + off : nullptr; off += gw_main;
   }
+  const int Bc = pl.Bc;
+  if (pl.S > 1) {
+    pl.seg_clouds = cv.take<float>((size_t)pl.M * c.nfeat);
+    pl.seg_T = cv.take<float>((size_t)Bc * 4);
+  }
   auto carve_segment = [&](Segment& sg, float* final_out) {
     for (size_t k = 0; k < sg.convs.size(); ++k) {
       Layer& l = pl.L[sg.convs[k]];
@@ -163,6 +187,12 @@ int make_plan(const spg_pointnet_cfg* cfg, int B, int training, void* ws, const 
     sg.ldpool = (lc.cout + sg.nextra + 3) & ~3;      // padded: rows readable as aligned float4
     sg.pooled = cv.take<float>((size_t)B * sg.ldpool);
     sg.aidx = cv.take<int>((size_t)B * sg.ldpool);
+    sg.spool = sg.pooled; sg.sidx = sg.aidx; sg.ldseg = sg.ldpool;
+    if (pl.S > 1) {
+      sg.ldseg = (lc.cout + 3) & ~3;
+      sg.spool = cv.take<float>((size_t)Bc * sg.ldseg);
+      sg.sidx = cv.take<int>((size_t)Bc * sg.ldseg);
+    }
     for (size_t k = 0; k < sg.fcs.size(); ++k) {
       Layer& l = pl.L[sg.fcs[k]];
       const bool last = k + 1 == sg.fcs.size();
@@ -172,18 +202,18 @@ int make_plan(const spg_pointnet_cfg* cfg, int B, int training, void* ws, const 
   };
   if (pl.has_stn) carve_segment(pl.stn, nullptr);
   carve_segment(pl.main, emb);
-  pl.stat = cv.take<float>((size_t)B * 4 * 2 * cmax);      // up to 4 per-wave partials per tile
-  pl.stat_cnt = cv.take<float>((size_t)B * 4 + 64);
+  pl.stat = cv.take<float>((size_t)Bc * 4 * 2 * cmax);      // up to 4 per-wave partials per tile
+  pl.stat_cnt = cv.take<float>((size_t)Bc * 4 + 64);
   pl.fin = cv.take<double>(spg_bn_finalize_scratch_doubles(cmax));
-  pl.pmax = cv.take<float>((size_t)B * 4 * cmax); pl.pmin = cv.take<float>((size_t)B * 4 * cmax);
-  pl.imax = cv.take<int>((size_t)B * 4 * cmax); pl.imin = cv.take<int>((size_t)B * 4 * cmax);
+  pl.pmax = cv.take<float>((size_t)Bc * 4 * cmax); pl.pmin = cv.take<float>((size_t)Bc * 4 * cmax);
+  pl.imax = cv.take<int>((size_t)Bc * 4 * cmax); pl.imin = cv.take<int>((size_t)Bc * 4 * cmax);
   pl.bytes = cv.off + 256;
   return 0;
 }
 
 SpgOperand op_cloud(const Plan& pl, const float* clouds, const float* stnT) {
   SpgOperand o; memset(&o, 0, sizeof(o));
-  o.mode = SPG_PRO_CLOUD; o.X = clouds; o.Ctot = pl.cfg.nfeat; o.P = pl.P; o.stnT = stnT;
+  o.mode = SPG_PRO_CLOUD; o.X = clouds; o.Ctot = pl.cfg.nfeat; o.P = pl.Pc; o.stnT = stnT;
   return o;
 }
 
@@ -215,7 +245,7 @@ SpgDenseBn bn_of(const Plan& pl, int update_times, float* stat, double* fin, flo
 bool fused_eval_convs(Plan& pl, Segment& sg, const float* clouds, const float* stnT, SpgConvStackParams& cp) {
   if (pl.training || sg.convs.size() > SPG_CONVSTACK_MAX_LAYERS) return false;
   memset(&cp, 0, sizeof(cp));
-  cp.clouds = clouds; cp.stnT = stnT; cp.B = pl.B; cp.P = pl.P; cp.Ctot = pl.cfg.nfeat; cp.nlayers = (int)sg.convs.size();
+  cp.clouds = clouds; cp.stnT = stnT; cp.B = pl.Bc; cp.P = pl.Pc; cp.Ctot = pl.cfg.nfeat; cp.nlayers = (int)sg.convs.size();
   for (size_t k = 0; k < sg.convs.size(); ++k) {
     const Layer& l = pl.L[sg.convs[k]];
     if (!l.bn) return false;
@@ -232,8 +262,15 @@ int forward_segment(Plan& pl, Segment& sg, const float* clouds, const float* stn
   if (fused) {
     const Layer& ll = pl.L[sg.convs.back()];
     SPG_TRY(spg_launch_conv_stack_eval(cp, st));
-    SPG_TRY(spg_launch_pool_select_parts(pl.pmax, pl.pmin, nullptr, nullptr, ll.s, pl.B, ll.cout, 4, sg.extra, sg.nextra,
-                                         sg.pooled, sg.ldpool, nullptr, st));
+    if (pl.S > 1) {      // per pseudo-superpoint first, then over the segments of a superpoint (no winners: nothing reads them)
+      SPG_TRY(spg_launch_pool_select_parts(pl.pmax, pl.pmin, nullptr, nullptr, ll.s, pl.Bc, ll.cout, 4, nullptr, 0, sg.spool, sg.ldseg,
+                                           nullptr, st));
+      SPG_TRY(spg_launch_pool_merge(sg.spool, nullptr, sg.ldseg, ll.s, pl.B, pl.S, pl.Pc, ll.cout, sg.extra, sg.nextra, sg.pooled,
+                                    nullptr, sg.ldpool, st));
+    } else {
+      SPG_TRY(spg_launch_pool_select_parts(pl.pmax, pl.pmin, nullptr, nullptr, ll.s, pl.B, ll.cout, 4, sg.extra, sg.nextra,
+                                           sg.pooled, sg.ldpool, nullptr, st));
+    }
   }
   size_t kfirst = 0;
   if (pl.training && sg.gram != nullptr) gram_record(sg.gram, false);      // (set below when this forward fills the Gram slots)
@@ -242,13 +279,13 @@ int forward_segment(Plan& pl, Segment& sg, const float* clouds, const float* stn
   if (!fused && pl.training && pl.fold && sg.gram != nullptr && sg.convs.size() > 2) {
     Layer& l0 = pl.L[sg.convs[0]];
     Layer& l1 = pl.L[sg.convs[1]];
-    if (l0.bn && l1.bn && spg_narrow_pair_supported(l0.cin, l0.cout, l1.cout, pl.P, pl.M)) {
+    if (l0.bn && l1.bn && spg_narrow_pair_supported(l0.cin, l0.cout, l1.cout, pl.Pc, pl.M)) {
       SpgGramParams gp; memset(&gp, 0, sizeof(gp));
-      gp.clouds = clouds; gp.stnT = stnT; gp.B = pl.B; gp.P = pl.P; gp.Ctot = pl.cfg.nfeat; gp.nfeat = l0.cin; gp.gram = sg.gram;
+      gp.clouds = clouds; gp.stnT = stnT; gp.B = pl.Bc; gp.P = pl.Pc; gp.Ctot = pl.cfg.nfeat; gp.nfeat = l0.cin; gp.gram = sg.gram;
       SPG_TRY(spg_launch_cloud_gram(gp, st));
       SPG_TRY(spg_slot_sync_after(sg.gram, spg_gram_slot_words(l0.cin), st, false));      // (slot-synchronised BatchNorm)
       SpgNarrowPairParams np; memset(&np, 0, sizeof(np));
-      np.clouds = clouds; np.stnT = stnT; np.P = pl.P; np.Ctot = pl.cfg.nfeat; np.nfeat = l0.cin; np.nblk = (int)(pl.M / 32);
+      np.clouds = clouds; np.stnT = stnT; np.P = pl.Pc; np.Ctot = pl.cfg.nfeat; np.nfeat = l0.cin; np.nblk = (int)(pl.M / 32);
       np.count = (double)pl.M;
       np.W1 = l0.W; np.b1 = l0.b; np.y1 = l0.y; np.gram = sg.gram; np.gamma1 = l0.gamma; np.beta1 = l0.beta; np.rm1 = l0.rm; np.rv1 = l0.rv;
       np.mean1 = l0.mean; np.rstd1 = l0.rstd; np.s1 = l0.s; np.t1 = l0.t;
@@ -267,17 +304,20 @@ int forward_segment(Plan& pl, Segment& sg, const float* clouds, const float* stn
     g.a = input_operand(pl, sg, false, k, clouds, stnT);
     if (k > 0 && pl.fold) g.fold = spg_fold_of(pl.L[sg.convs[k - 1]], pl.M, update_times, pl.cfg.bn_momentum, pl.cfg.bn_eps);
     g.W = l.W; g.ldw = l.cin; g.bias = l.b; g.M = (int)pl.M; g.N = l.cout; g.K = l.cin;
-    g.rows_per_tile = pl.P; g.epi = SPG_EPI_FWD; g.Y = l.y; g.ldy = l.ldy;
+    g.rows_per_tile = pl.Pc; g.epi = SPG_EPI_FWD; g.Y = l.y; g.ldy = l.ldy;
     if (l.Wb_f != nullptr) { g.Wb = l.Wb_f; g.ldwb = spg_split_ld(l.cin); g.wb_part_bytes = (long)l.cout * g.ldwb * 2; }
     if (last && !pl.training) g.Y = nullptr;     // inference: only the pooled values of the last conv are consumed
     g.stat = pl.training ? pl.stat : nullptr; g.stat_cnt = pl.stat_cnt;
     if (pl.fold) { g.stat = nullptr; g.stat_slots = l.slots; }
     int nparts = 0;
     if (last) {      // max-pool fused into the epilogue: the sign of the BatchNorm scale is the sign of gamma
-      g.pool_out = sg.pooled; g.pool_idx = sg.aidx; g.pool_ld = sg.ldpool; g.pool_sign = l.gamma;
-      g.pool_extra = sg.extra; g.pool_nextra = sg.nextra;
+      g.pool_out = sg.spool; g.pool_idx = sg.sidx; g.pool_ld = sg.ldseg; g.pool_sign = l.gamma;
+      if (pl.S == 1) { g.pool_extra = sg.extra; g.pool_nextra = sg.nextra; }      // (else appended by the merge)
     }
     SPG_TRY(spg_launch_gemm(g, st, &nparts));
+    if (last && pl.S > 1)      // the segments' extrema -> the superpoint's, by the epilogue's rule (the sign of gamma)
+      SPG_TRY(spg_launch_pool_merge(sg.spool, sg.sidx, sg.ldseg, l.gamma, pl.B, pl.S, pl.Pc, l.cout, sg.extra, sg.nextra, sg.pooled,
+                                    sg.aidx, sg.ldpool, st));
     if (pl.training && !pl.fold)      // (eval mode: one spg_launch_bn_eval_batch at the start of the forward)
       SPG_TRY(spg_launch_bn_finalize(pl.stat, pl.stat_cnt, nparts, pl.M, l.cout, l.gamma, l.beta, l.rm, l.rv,
                                      pl.cfg.bn_momentum, pl.cfg.bn_eps, update_times, l.mean, l.rstd, l.s, l.t, pl.fin, st));
@@ -319,6 +359,10 @@ struct BwdScratch {
   float* stat = nullptr;                    // [ntile][2][cmax]
   float* dxy = nullptr;                     // [M, 2]
   float* dT = nullptr;                      // [B, 4]
+  // npts > 128 (spg_segments.h): the pooled gradient and the winners in the segments' view [Bc, ldseg]; per-segment partials [Bc, 4] of dT
+  float* gseg = nullptr;
+  int* lidx = nullptr;
+  float* dTseg = nullptr;
   float* grad_global = nullptr;             // optional output [B, nextra]: gradient wrt the concatenated global features
   size_t bytes = 0;
 };
@@ -335,16 +379,21 @@ void carve_bwd(const Plan& pl, void* ws, BwdScratch& s) {
     // every layer gets its own slice of the reduction arena (partials stay alive until the single batched reduce)
     workmax += spg_queue_layer_floats(l.conv ? pl.M : pl.B, l.cout, l.cin);
     // (the one-pass backward of a segment's first convolution writes one partial per wave, spg_narrow.h)
-    if (l.conv && l.cin <= SPG_GRAM_MAXF) workmax += ((size_t)spg_first_conv_bwd_partials(pl.B) * l.cout * l.cin + 63) & ~(size_t)63;
+    if (l.conv && l.cin <= SPG_GRAM_MAXF) workmax += ((size_t)spg_first_conv_bwd_partials(pl.Bc) * l.cout * l.cin + 63) & ~(size_t)63;
   }
   s.dzA = cv.take<float>((size_t)pl.M * cconv); s.dzB = cv.take<float>((size_t)pl.M * cconv);
   s.fzA = cv.take<float>((size_t)pl.B * cfc); s.fzB = cv.take<float>((size_t)pl.B * cfc);
   s.consts = cv.take<float>((size_t)4 * cmax);
   s.fin = cv.take<double>(spg_bn_finalize_scratch_doubles(cmax));
   s.work = cv.take<float>(workmax); s.work_floats = workmax;
-  s.stat = cv.take<float>((size_t)pl.B * 4 * 2 * cmax);
+  s.stat = cv.take<float>((size_t)pl.Bc * 4 * 2 * cmax);
   s.dxy = cv.take<float>((size_t)pl.M * 2);
   s.dT = cv.take<float>((size_t)pl.B * 4);
+  if (pl.S > 1) {
+    const size_t ldmax = pl.has_stn && pl.stn.ldseg > pl.main.ldseg ? pl.stn.ldseg : pl.main.ldseg;      // (the stacks run one after the other)
+    s.gseg = cv.take<float>((size_t)pl.Bc * ldmax); s.lidx = cv.take<int>((size_t)pl.Bc * ldmax);
+    s.dTseg = cv.take<float>((size_t)pl.Bc * 4);
+  }
   s.bytes = cv.off + 256;
 }
 
@@ -362,6 +411,7 @@ int backward_segment(Plan& pl, Segment& sg, BwdScratch& s, SpgReduceQueue& rq, S
   // leave as ONE grouped launch (spg_gemm.h) -- three launches per head instead of six (spg_dense_backward).
   float* fz[2] = {s.fzA, s.fzB};
   int flip = 0;
+  const float* pooled_grad = nullptr;
   {
   SpgGroupScope grp(st);
   // the split partials the launches so far have queued (the other segment's weight gradients: ~100 MB, 2/3 of the step's final
@@ -389,12 +439,15 @@ int backward_segment(Plan& pl, Segment& sg, BwdScratch& s, SpgReduceQueue& rq, S
       cur = spg_op_bnbwd(out, prod.y, prod.ldy, s.consts, C);
     } else {
       memset(&cur, 0, sizeof(cur));
-      cur.mode = SPG_PRO_POOLBWD; cur.X = out; cur.ldg = (int)sg.ldpool; cur.aidx = sg.aidx; cur.P = pl.P;
+      cur.mode = SPG_PRO_POOLBWD; cur.X = out; cur.ldg = (int)sg.ldpool; cur.aidx = sg.aidx; cur.P = pl.Pc;
+      if (pl.S > 1) { cur.X = s.gseg; cur.ldg = (int)sg.ldseg; cur.aidx = s.lidx; pooled_grad = out; }      // (filled behind the head, below)
       cur.X2 = prod.y; cur.ld = prod.ldy;
       cur.c0 = s.consts; cur.c1 = s.consts + C; cur.c2 = s.consts + 2 * C; cur.c3 = s.consts + 3 * C;
     }
   }
   }      // (the group scope ends with the head: the convolutions' launches are ordered, never grouped)
+  if (pl.S > 1)      // the head's pooled gradient [B, ldpool] and the merged winners -> what the POOLBWD operand reads per pseudo-superpoint
+    SPG_TRY(spg_launch_pool_expand(pooled_grad, sg.aidx, sg.ldpool, B, pl.S, pl.Pc, pl.L[sg.convs.back()].cout, s.gseg, s.lidx, sg.ldseg, st));
   // ---- conv stack ----
   float* dz[2] = {s.dzA, s.dzB};
   flip = 0;
@@ -406,7 +459,7 @@ int backward_segment(Plan& pl, Segment& sg, BwdScratch& s, SpgReduceQueue& rq, S
       float* out = dz[flip];
       SpgGemmParams g; memset(&g, 0, sizeof(g));
       g.a = cur; g.W = l.W; g.ldw = l.cin; g.w_red = 1;
-      g.M = (int)pl.M; g.N = l.cin; g.K = l.cout; g.rows_per_tile = pl.P;
+      g.M = (int)pl.M; g.N = l.cin; g.K = l.cout; g.rows_per_tile = pl.Pc;
       g.epi = SPG_EPI_BWD; g.Y = out; g.ldy = l.cin; g.Yp = prod.y; g.ldyp = prod.ldy;
       g.ms = prod.s; g.mt = prod.t; g.mask_relu = 1; g.n_mask = prod.cout;
       g.mmean = prod.mean; g.mrstd = prod.rstd; g.stat_slots = prod.slots_bwd; g.fold_bwd = pending;
@@ -425,13 +478,14 @@ int backward_segment(Plan& pl, Segment& sg, BwdScratch& s, SpgReduceQueue& rq, S
     // cloud; the layer's raw output is not read (it is linear in the cloud: its part collapses onto the Gram matrix)
     if (k == 0 && pl.fold && sg.gram != nullptr && gram_recorded(sg.gram) && sg.convs.size() > 2 && pending.slots != nullptr && cur.mode == SPG_PRO_BNBWD &&
         cur.ld == l.cout && cur.c0 == s.consts && (!want_dxy || dT_out != nullptr) &&
-        spg_narrow_pair_supported(l.cin, l.cout, pl.L[sg.convs[1]].cout, pl.P, pl.M) && spg_first_conv_bwd_supported(l.cin, l.cout, pl.P, pl.M)) {
+        spg_narrow_pair_supported(l.cin, l.cout, pl.L[sg.convs[1]].cout, pl.Pc, pl.M) && spg_first_conv_bwd_supported(l.cin, l.cout, pl.Pc, pl.M)) {
       SpgFirstConvBwdParams fp; memset(&fp, 0, sizeof(fp));
-      fp.clouds = clouds; fp.stnT = stnT; fp.B = pl.B; fp.P = pl.P; fp.Ctot = pl.cfg.nfeat; fp.nfeat = l.cin;
+      fp.clouds = clouds; fp.stnT = stnT; fp.B = pl.Bc; fp.P = pl.Pc; fp.Ctot = pl.cfg.nfeat; fp.nfeat = l.cin;
       fp.g = cur.X; fp.W1 = l.W; fp.gram = sg.gram; fp.fold = pending; memset(&pending, 0, sizeof(pending));
-      fp.dT = want_dxy ? dT_out : nullptr;
-      SPG_TRY(spg_queue_partials(rq, spg_first_conv_bwd_partials(pl.B), l.cout * l.cin, l.dW, &fp.partial, st));
+      fp.dT = want_dxy ? (pl.S > 1 ? s.dTseg : dT_out) : nullptr;
+      SPG_TRY(spg_queue_partials(rq, spg_first_conv_bwd_partials(pl.Bc), l.cout * l.cin, l.dW, &fp.partial, st));
       SPG_TRY(spg_launch_first_conv_bwd(fp, st));
+      if (want_dxy && pl.S > 1) SPG_TRY(spg_launch_segment_dT_sum(s.dTseg, B, pl.S, dT_out, st));      // (segments in fixed order)
       if (l.db) SPG_TRY(spg_zero_bytes_async(l.db, sizeof(float) * l.cout, st));
       if (want_dxy && dT_done != nullptr) *dT_done = true;
       continue;
@@ -447,7 +501,7 @@ int backward_segment(Plan& pl, Segment& sg, BwdScratch& s, SpgReduceQueue& rq, S
       float* out = dz[flip]; flip ^= 1;
       SpgGemmParams g; memset(&g, 0, sizeof(g));
       g.a = cur; g.W = l.W; g.ldw = l.cin; g.w_red = 1;
-      g.M = (int)pl.M; g.N = l.cin; g.K = l.cout; g.rows_per_tile = pl.P;
+      g.M = (int)pl.M; g.N = l.cin; g.K = l.cout; g.rows_per_tile = pl.Pc;
       if (l.Wb_t != nullptr) { g.Wb = l.Wb_t; g.ldwb = spg_split_ld(l.cout); g.wb_part_bytes = (long)l.cin * g.ldwb * 2; }
       g.epi = SPG_EPI_BWD; g.Y = out; g.ldy = l.cin; g.Yp = prod.y; g.ldyp = prod.ldy;
       g.ms = prod.s; g.mt = prod.t; g.mask_relu = 1; g.n_mask = prod.cout;
@@ -465,7 +519,7 @@ int backward_segment(Plan& pl, Segment& sg, BwdScratch& s, SpgReduceQueue& rq, S
       // gradient wrt the transformed xy only (learning/pointnet.py:123-124): 2 output columns
       SpgGemmParams g; memset(&g, 0, sizeof(g));
       g.a = cur; g.W = l.Wpad ? l.Wpad : l.W; g.ldw = l.Wpad ? l.ldw : l.cin; g.w_red = 1;
-      g.M = (int)pl.M; g.N = 2; g.K = l.cout; g.rows_per_tile = pl.P;
+      g.M = (int)pl.M; g.N = 2; g.K = l.cout; g.rows_per_tile = pl.Pc;
       g.epi = SPG_EPI_BWD; g.Y = s.dxy; g.ldy = 2;
       SPG_TRY(spg_launch_gemm(g, st));
     }
@@ -526,16 +580,24 @@ extern "C" int spg_pointnet_forward_ext(const spg_pointnet_cfg* cfg, int B, cons
   }
   // train mode: the BatchNorm statistics travel as slots from each producer GEMM to its consumer; every tile
   // contributes at most 4 wave partials per channel: within the slots' capacity up to ~500 k superpoints
-  pl.fold = pl.training && spg_bn_fold_allowed(4L * B);
+  pl.fold = pl.training && spg_bn_fold_allowed(4L * pl.Bc);
   SPG_TRY(spg_bn_slot_sync_check(pl.training, pl.fold, "slot-synchronised BatchNorm needs the statistics slots (spg_tune key 10 off, batch within the slots' capacity)"));
   if (pl.training && !g_slots_clean) {      // always in train mode: the backward decides about its own slots independently (they are cleared here too)
     hipError_t me = hipMemsetAsync(pl.slots_all, 0, pl.slots_words * sizeof(unsigned long long), st);
     if (me != hipSuccess) { spg_set_error("hipMemsetAsync: %s", hipGetErrorString(me)); return (int)me; }
   }
   const float* stnT = ext_transform;      // [B, 4] = T - I of an externally evaluated STN (LocalCloudEmbedder), or null
+  if (pl.S > 1) {      // npts > 128: the convolutions read the clouds per segment (spg_segments.h); the backward reads the same copy
+    SPG_TRY(spg_launch_segment_clouds(clouds, B, pl.cfg.nfeat, pl.P, pl.Pc, pl.seg_clouds, st));
+    clouds = pl.seg_clouds;
+  }
   if (pl.has_stn) {
     SPG_TRY(forward_segment(pl, pl.stn, clouds, nullptr, bn_update_times, st));
     stnT = pl.L[pl.stn.fcs.back()].y;
+  }
+  if (pl.S > 1 && stnT != nullptr) {      // a superpoint's transform for each of its segments
+    SPG_TRY(spg_launch_segment_transforms(stnT, B, pl.S, pl.seg_T, st));
+    stnT = pl.seg_T;
   }
   SPG_TRY(forward_segment(pl, pl.main, clouds, stnT, bn_update_times, st));
   return 0;
@@ -592,11 +654,16 @@ extern "C" int spg_pointnet_backward_ext(const spg_pointnet_cfg* cfg, int B, con
   // the forward wrote the last fc output to `emb`; it is not needed by the backward, so pass a dummy
   SPG_TRY(make_plan(cfg, B, 1, workspace, params, (float*)grad_emb /*unused as y*/, pl));
   pl.main.extra = clouds_global;
-  pl.fold = spg_bn_fold_allowed(4L * B);
+  pl.fold = spg_bn_fold_allowed(4L * pl.Bc);
   for (size_t i = 0; i < pl.L.size(); ++i) spg_dense_bind_grads(pl.L[i], grads + 6 * i);
   BwdScratch s;
   carve_bwd(pl, bwd_workspace, s);
   const float* stnT = pl.has_stn ? pl.L[pl.stn.fcs.back()].y : ext_transform;
+  const float* clouds_pts = clouds;      // [B, nfeat, P]: spg_launch_stn_dT walks the true P points of a superpoint (rows b * P + p of dxy)
+  if (pl.S > 1) {      // the forward's copies in the segments' view
+    clouds = pl.seg_clouds;
+    if (stnT != nullptr) stnT = pl.seg_T;
+  }
   const int cout = pl.L[pl.main.fcs.back()].cout;
   SpgReduceQueue rq;
   rq.arena = s.work; rq.arena_floats = s.work_floats;
@@ -606,9 +673,9 @@ extern "C" int spg_pointnet_backward_ext(const spg_pointnet_cfg* cfg, int B, con
   SPG_TRY(backward_segment(pl, pl.main, s, rq, spg_op_ident(grad_emb, cout), clouds, stnT, pl.has_stn || grad_transform != nullptr, st, false,
                            dT_target, &dT_done));
   if (grad_transform != nullptr && !dT_done)      // gradient wrt the external 2x2 transforms (learning/pointnet.py:196-198)
-    SPG_TRY(spg_launch_stn_dT(clouds, pl.cfg.nfeat, pl.P, B, s.dxy, 2, grad_transform, st));
+    SPG_TRY(spg_launch_stn_dT(clouds_pts, pl.cfg.nfeat, pl.P, B, s.dxy, 2, grad_transform, st));
   if (pl.has_stn) {
-    if (!dT_done) SPG_TRY(spg_launch_stn_dT(clouds, pl.cfg.nfeat, pl.P, B, s.dxy, 2, s.dT, st));
+    if (!dT_done) SPG_TRY(spg_launch_stn_dT(clouds_pts, pl.cfg.nfeat, pl.P, B, s.dxy, 2, s.dT, st));
     SPG_TRY(backward_segment(pl, pl.stn, s, rq, spg_op_ident(s.dT, 4), clouds, nullptr, false, st, true));
   }
   if (g_slots_clear_at_end && pl.slots_all != nullptr && pl.slots_words > 0) {

@@ -92,7 +92,7 @@ def build_parser():
     a('--spg_superedge_cutoff', default=-1, type=float, help='Artificially constrained maximum length of superedge, -1=do not constrain')
     # PointNet
     a('--ptn_minpts', default=40, type=int, help='Minimum number of points in a superpoint for computing its embedding.')
-    a('--ptn_npts', default=128, type=int, help='Number of input points for PointNet.')
+    a('--ptn_npts', default=128, type=int, help='Number of input points for PointNet: up to 128, or below 4096 with a divisor in [32, 128] (256, 384, 512, 160, 1000, ...).')
     a('--ptn_widths', default='[[64,64,128,128,256], [256,64,32]]', help='PointNet widths')
     a('--ptn_widths_stn', default='[[64,64,128], [128,64]]', help='PointNet\'s Transformer widths')
     a('--ptn_nfeat_stn', default=11, type=int, help='PointNet\'s Transformer number of input features')

@@ -95,6 +95,7 @@ class STNkD(_LayerTable):
 
     def _cfg(self, npts):
         bn0 = self.convs[1]
+        ops.model.pointnet_segments(npts)      # NotImplementedError with the rule for an npts the kernels do not serve
         return ops.make_pointnet_cfg(self._nfeat, 0, 0, npts, [], [], self._nf_conv, self._nf_fc + [self._K * self._K], False,
                                      bn0.eps, _layers.bn_momentum(bn0))
 
@@ -111,6 +112,7 @@ class STNkD(_LayerTable):
         if _groupnorm_spec(self) is not None:      # norm = 'layer' | 'group': the cloud-resident kernels (spg_groupnorm.hip)
             out = _GroupNormFunction.apply(self, rows, input, None, None, *_layers.flat_params(rows))
         else:
+            self._cfg(input.shape[2])      # (an unsupported npts is refused here, before the batch counters move)
             if self.training:
                 self._bump_batches_tracked(1)
             out = _PointNetFunction.apply(self, rows, input, None, None, self.training, 1, *_layers.node_inputs(self, rows, input.device))
@@ -200,6 +202,7 @@ class PointNet(_LayerTable):
     def _cfg(self, npts):
         cache = self.__dict__.setdefault('_cfg_cache', {})
         if npts not in cache:
+            ops.model.pointnet_segments(npts)      # NotImplementedError with the rule for an npts the kernels do not serve
             stn_conv = self.stn._nf_conv if self.nfeat_stn > 0 else []
             stn_fc = self.stn._nf_fc if self.nfeat_stn > 0 else []
             bn0 = self.convs[1]
@@ -233,6 +236,7 @@ class PointNet(_LayerTable):
         input, rows = input.contiguous().float(), self._groups_tensors()
         if self._gn_spec() is not None:      # norm = 'layer' | 'group': the cloud-resident kernels (spg_groupnorm.hip)
             return _GroupNormFunction.apply(self, rows, input, input_global, None, *_layers.flat_params(rows))
+        self._cfg(input.shape[2])      # (an unsupported npts is refused here, before the batch counters move)
         if self.training:
             self._bump_batches_tracked(bn_update_times)
         return _PointNetFunction.apply(self, rows, input, input_global, None, self.training, bn_update_times,

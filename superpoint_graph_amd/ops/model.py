@@ -245,6 +245,29 @@ def linear_backward(dy, x, w, need_dx=True, has_bias=True, out_w=None, out_b=Non
 # --------------------------------------------------------------------------------------------------
 # PointNet
 # --------------------------------------------------------------------------------------------------
+POINTNET_MAX_TILE = 128          # points of one row tile of the convolutions
+POINTNET_MIN_SEGMENT = 32        # shortest segment a superpoint of more than 128 points may be cut into
+POINTNET_NPTS_END = 4096         # from this size on nothing is served (the library's size queries have always refused 4096)
+POINTNET_NPTS_RULE = (f'npts must be in [1, {POINTNET_MAX_TILE}], or in ({POINTNET_MAX_TILE}, {POINTNET_NPTS_END}) with a divisor in '
+                      f'[{POINTNET_MIN_SEGMENT}, {POINTNET_MAX_TILE}] (the largest one is the segment length: 256 = 2 x 128, '
+                      '160 = 2 x 80, 1000 = 8 x 125; 131 and 262 have none)')
+
+
+def pointnet_segments(npts):
+    """(Ps, S): the BatchNorm PointNet runs its convolutions on S = npts / Ps segments of Ps points per superpoint -- one segment up
+    to 128 points, else (below 4096) Ps is the largest divisor of npts that is <= 128 and must be >= 32 (the library
+    refuses the same with -2).  NotImplementedError that states the rule: pointnet_forward and the modules call this before anything is
+    allocated or launched (make_pointnet_cfg fills any npts in, as it always did)."""
+    npts = int(npts)
+    if 1 <= npts <= POINTNET_MAX_TILE:
+        return npts, 1
+    if POINTNET_MAX_TILE < npts < POINTNET_NPTS_END:
+        for ps in range(POINTNET_MAX_TILE, POINTNET_MIN_SEGMENT - 1, -1):
+            if npts % ps == 0:
+                return ps, npts // ps
+    raise NotImplementedError(f'PointNet: npts = {npts} is not supported: {POINTNET_NPTS_RULE}')
+
+
 def make_pointnet_cfg(nfeat, nfeat_stn, nfeat_global, npts, stn_conv, stn_fc, conv, fc, last_ac=False,
                       bn_eps=1e-5, bn_momentum=0.1) -> PointNetCfg:
     c = PointNetCfg()
@@ -299,6 +322,7 @@ def pointnet_forward(cfg: PointNetCfg, clouds, clouds_global, groups: List[Seque
     of include/spg_hip.h.  ext_transform: [B, 4] = T - I of an externally evaluated STN (PointNet without inner STN).
     Returns (emb [B, D], PointNetState)."""
     _req(clouds, torch.float32, 'clouds')
+    pointnet_segments(cfg.npts)      # an unsupported npts: NotImplementedError with the rule, before any allocation or launch
     B = clouds.shape[0]
     if clouds.shape[1] != cfg.nfeat or clouds.shape[2] != cfg.npts:
         raise ValueError(f'clouds must be [B, {cfg.nfeat}, {cfg.npts}], got {tuple(clouds.shape)}')
