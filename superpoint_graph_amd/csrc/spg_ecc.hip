@@ -583,10 +583,12 @@ int spg_launch_ecc_step_fwd(const SpgEccStepFwd& p, hipStream_t stream) {
 // GRUCellEx backward for one node (one wavefront): recompute of the forward from (aggregate sa[0..31], state sh[0..31]),
 // gate gradients stored for the deferred weight-gradient GEMMs, returns the gradient wrt the hidden state (direct path,
 // dh_acc) and wrt the aggregate (da), lanes 0..31.  sa / sh are GW = 96 floats each (re-used for dgi / dgh), sx and sd 32;
-// sw is the workgroup's padded copy of the cell weights.
+// sw is the workgroup's padded copy of the cell weights.  DEPTH / DEPTH_IG: gate rows per batch of LDS reads in the W^T / input-gate
+// products -- 2 (1) registers per row plus the operand quads, so as deep as the instantiation's registers allow (24 / 32 with one
+// workgroup per CU, 16 everywhere else -- 4 made the iteration-major backward 2 % slower: profiles/ecc_cell_lds_{isa,ab}.txt).
 struct SpgGruBwdOut { float *dgi, *dgh, *dui, *duh, *dpre, *xg; long ld96, ld32; };
 
-template <bool WAVE, int UNR = 8>
+template <bool WAVE, int DEPTH = 16, int DEPTH_IG = DEPTH>
 __device__ __forceinline__ void spg_gru_backward_node(const SpgGruParams& G, const float* __restrict__ sw, float* sa, float* sh,
                                                       float* sx, float* sd, int lane, bool active, long j, float dH,
                                                       const SpgGruBwdOut& o, float& dh_acc, float& da,
@@ -661,16 +663,42 @@ __device__ __forceinline__ void spg_gru_backward_node(const SpgGruParams& G, con
     // W^T products dx[c] = sum_o W_ih[o][c] dgi[o], dh[c] += sum_o W_hh[o][c] dgh[o]: the 96 gate rows are split over the two
     // half-waves (48 each) and over two accumulators, so the dependent fma chain is 24 long instead of 96; the halves meet
     // through one cross-row shuffle
+    //
+    // The LDS reads of a product are issued in BATCHES of DEPTH gate rows (weights: one value per row and matrix, by column;
+    // operands: contiguous, 128-bit broadcasts), all of a batch in front of its multiply-adds, and the loop counter is the same
+    // for every lane (the half-wave's first row is in the addresses).  Written as one load-use loop from a per-lane first row,
+    // the compiler built a divergent loop plus a remainder loop and waited for every pair of weights where it was used: 64
+    // dependent LDS round trips per node and iteration for 128 multiply-adds per lane, with one wavefront per SIMD and nothing
+    // to switch to.  The empty asm statements behind a batch keep the reads from sinking back to their uses.  Every
+    // multiply-add, its operands and the order within each of the four accumulator chains are unchanged: bit-identical.
     float dx;
     {
+      static_assert(DEPTH % 4 == 0 && 48 % DEPTH == 0, "whole batches of operand quads per half-wave");
       const int c = lane & 31, q0 = 48 * (lane >> 5);
+      const float* wi = sw_ih + q0 * SPG_WLD + c;
+      const float* wh = sw_hh + q0 * SPG_WLD + c;
+      const f32x4* pa = reinterpret_cast<const f32x4*>(sa + q0);
+      const f32x4* ph = reinterpret_cast<const f32x4*>(sh + q0);
       float x0 = 0.f, x1 = 0.f, h0 = 0.f, h1 = 0.f;
-#pragma unroll UNR
-      for (int q = q0; q < q0 + 48; q += 2) {
-        x0 = fmaf(sw_ih[q * SPG_WLD + c], sa[q], x0);
-        x1 = fmaf(sw_ih[(q + 1) * SPG_WLD + c], sa[q + 1], x1);
-        h0 = fmaf(sw_hh[q * SPG_WLD + c], sh[q], h0);
-        h1 = fmaf(sw_hh[(q + 1) * SPG_WLD + c], sh[q + 1], h1);
+#pragma unroll
+      for (int t0 = 0; t0 < 48; t0 += DEPTH) {
+        float wiv[DEPTH], whv[DEPTH];
+        f32x4 av[DEPTH / 4], hv[DEPTH / 4];
+#pragma unroll
+        for (int k = 0; k < DEPTH; ++k) { wiv[k] = wi[(t0 + k) * SPG_WLD]; whv[k] = wh[(t0 + k) * SPG_WLD]; }
+#pragma unroll
+        for (int k = 0; k < DEPTH / 4; ++k) { av[k] = pa[t0 / 4 + k]; hv[k] = ph[t0 / 4 + k]; }
+#pragma unroll
+        for (int k = 0; k < DEPTH; ++k) { asm volatile("" : "+v"(wiv[k])); asm volatile("" : "+v"(whv[k])); }
+#pragma unroll
+        for (int k = 0; k < DEPTH / 4; ++k) { asm volatile("" : "+v"(av[k])); asm volatile("" : "+v"(hv[k])); }
+#pragma unroll
+        for (int k = 0; k < DEPTH; k += 2) {
+          x0 = fmaf(wiv[k], av[k >> 2][k & 3], x0);
+          x1 = fmaf(wiv[k + 1], av[k >> 2][(k & 3) + 1], x1);
+          h0 = fmaf(whv[k], hv[k >> 2][k & 3], h0);
+          h1 = fmaf(whv[k + 1], hv[k >> 2][(k & 3) + 1], h1);
+        }
       }
       float xs = x0 + x1, hs_ = h0 + h1;
       xs += __shfl_xor(xs, 32, 64);
@@ -688,10 +716,27 @@ __device__ __forceinline__ void spg_gru_backward_node(const SpgGruParams& G, con
     spg_node_sync<WAVE>();
     if (G.ingate && lane < 32) {
       float g0 = 0.f, g1 = 0.f;
-#pragma unroll UNR
-      for (int q = 0; q < 32; q += 2) {
-        g0 = fmaf(sw_ig[q * SPG_WLD + lane], sd[q], g0);
-        g1 = fmaf(sw_ig[(q + 1) * SPG_WLD + lane], sd[q + 1], g1);
+      constexpr int DG = DEPTH_IG;      // (the same batching: DG rows of W_ig by column, the operand as 128-bit broadcasts)
+      static_assert(DG % 4 == 0 && 32 % DG == 0, "whole batches of operand quads");
+      const float* wg = sw_ig + lane;
+      const f32x4* pd = reinterpret_cast<const f32x4*>(sd);
+#pragma unroll
+      for (int t0 = 0; t0 < 32; t0 += DG) {
+        float wgv[DG];
+        f32x4 dv[DG / 4];
+#pragma unroll
+        for (int k = 0; k < DG; ++k) wgv[k] = wg[(t0 + k) * SPG_WLD];
+#pragma unroll
+        for (int k = 0; k < DG / 4; ++k) dv[k] = pd[t0 / 4 + k];
+#pragma unroll
+        for (int k = 0; k < DG; ++k) asm volatile("" : "+v"(wgv[k]));
+#pragma unroll
+        for (int k = 0; k < DG / 4; ++k) asm volatile("" : "+v"(dv[k]));
+#pragma unroll
+        for (int k = 0; k < DG; k += 2) {
+          g0 = fmaf(wgv[k], dv[k >> 2][k & 3], g0);
+          g1 = fmaf(wgv[k + 1], dv[k >> 2][(k & 3) + 1], g1);
+        }
       }
       dh_acc += g0 + g1;
     }
@@ -1071,6 +1116,19 @@ __device__ __forceinline__ void spg_px_rows_init(GruRowsReg& w, const GruRowsLds
 __device__ __forceinline__ void spg_px_rows_init(GruRowsLds& w, const GruRowsLds& l) { w = l; }
 
 // ---- the head behind the recurrence (SpgEccHead, spg_ecc.h): classifier + weighted cross entropy per node, in the owning wave ----
+// The four 64-lane float64 butterflies of a thread, step by step SIDE BY SIDE: the four exchanges of a step are independent and share
+// one LDS-crossbar round trip (as four loops in a row they were 24 dependent round trips of two ds_bpermute each at the forward's
+// entry); each sum keeps its own pairwise order, so its bits.
+__device__ __forceinline__ void spg_wave_sum4_f64(double (&acc)[4]) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    double o[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) o[q] = __shfl_xor(acc[q], off, 64);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc[q] += o[q];
+  }
+}
 // Sum over ALL rows of the labelled rows' class weights -- the normaliser of the mean reduction -- by the 256 threads of a
 // workgroup, with the summation order of ce_fwd_kernel (spg_loss.hip): 1024 virtual threads striding the rows, a 64-lane butterfly
 // per virtual wave, the 16 wave sums added in order.  Thread p plays the virtual threads p, p + 256, p + 512, p + 768 (virtual
@@ -1099,11 +1157,10 @@ __device__ __forceinline__ void spg_px_head_wsum_partials(const SpgEccHead& hd, 
       if (i < hd.N && t[q] != hd.ignore_index && t[q] >= 0 && t[q] < hd.C) acc[q] += (double)w[q];
     }
   }
+  spg_wave_sum4_f64(acc);
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    for (int off = 32; off >= 1; off >>= 1) acc[q] += __shfl_xor(acc[q], off, 64);
+  for (int q = 0; q < 4; ++q)
     if ((threadIdx.x & 63) == 0) part[(threadIdx.x >> 6) + 4 * q] = acc[q];
-  }
 }
 // the same for N <= 1024 (one pass) in two steps: the label loads are issued by `labels` (in front of other staging work), the sums
 // follow in `from_labels` -- one dependent round trip behind them instead of two
@@ -1121,14 +1178,17 @@ __device__ __forceinline__ void spg_px_head_wsum_from_labels(const SpgEccHead& h
     const bool ok = t[q] != hd.ignore_index && t[q] >= 0 && t[q] < hd.C;
     w[q] = hd.class_weight ? hd.class_weight[ok ? t[q] : 0] : 1.f;
   }
+  double acc[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int i = (int)threadIdx.x + 256 * q;
-    double acc = 0.0;
-    if (i < hd.N && t[q] != hd.ignore_index && t[q] >= 0 && t[q] < hd.C) acc += (double)w[q];
-    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
-    if ((threadIdx.x & 63) == 0) part[(threadIdx.x >> 6) + 4 * q] = acc;
+    acc[q] = 0.0;
+    if (i < hd.N && t[q] != hd.ignore_index && t[q] >= 0 && t[q] < hd.C) acc[q] += (double)w[q];
   }
+  spg_wave_sum4_f64(acc);
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+    if ((threadIdx.x & 63) == 0) part[(threadIdx.x >> 6) + 4 * q] = acc[q];
 }
 __device__ __forceinline__ float spg_px_head_wsum_finish(const double* part) {
   double b = 0.0;
@@ -1488,14 +1548,28 @@ __global__ __launch_bounds__(256, WPC) void spg_ecc_persist_fwd_kernel(const Spg
       SPG_XP(2);
       if constexpr (MATRIX) {
         if (c0 == 0) {
+          // the neighbours' rows of ALL register-resident edges as one batch of LDS reads in front of the products (read under
+          // each edge's own branch, every edge was an LDS round trip of its own; a node has up to KMAX of them and the
+          // high-degree nodes are the ones an iteration waits for).  Rows u >= n are read too -- hs has SPG_PX_CH rows, stale
+          // ones may hold anything -- and their products stay SKIPPED, not multiplied by zero.
+          float xv[KMAX][4];
+#pragma unroll
+          for (int u = 0; u < KMAX; ++u) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) xv[u][q] = hs[u * 32 + kb + 8 * q];
+          }
+#pragma unroll
+          for (int u = 0; u < KMAX; ++u) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) asm volatile("" : "+v"(xv[u][q]));
+          }
 #pragma unroll
           for (int u = 0; u < KMAX; ++u) {
             if (u < n) {
 #pragma unroll
               for (int q = 0; q < 4; ++q) {
-                const float xv = hs[u * 32 + kb + 8 * q];
-                a4[0] = fmaf(xv, wc[u][q][0], a4[0]); a4[1] = fmaf(xv, wc[u][q][1], a4[1]);
-                a4[2] = fmaf(xv, wc[u][q][2], a4[2]); a4[3] = fmaf(xv, wc[u][q][3], a4[3]);
+                a4[0] = fmaf(xv[u][q], wc[u][q][0], a4[0]); a4[1] = fmaf(xv[u][q], wc[u][q][1], a4[1]);
+                a4[2] = fmaf(xv[u][q], wc[u][q][2], a4[2]); a4[3] = fmaf(xv[u][q], wc[u][q][3], a4[3]);
               }
             }
           }
@@ -1514,9 +1588,14 @@ __global__ __launch_bounds__(256, WPC) void spg_ecc_persist_fwd_kernel(const Spg
         }
       } else if (lane < 32) {
         if (c0 == 0) {
+          float xv[KMAX];      // (the same batch; one value per edge)
+#pragma unroll
+          for (int u = 0; u < KMAX; ++u) xv[u] = hs[u * 32 + lane];
+#pragma unroll
+          for (int u = 0; u < KMAX; ++u) asm volatile("" : "+v"(xv[u]));
 #pragma unroll
           for (int u = 0; u < KMAX; ++u)
-            if (u < n) a4[0] = fmaf(hs[u * 32 + lane], wv[u], a4[0]);
+            if (u < n) a4[0] = fmaf(xv[u], wv[u], a4[0]);
         }
         for (int u = (c0 == 0 ? KMAX : 0); u < n; ++u)
           a4[0] = fmaf(hs[u * 32 + lane], p.W[(long)(e0 + c0 + u) * 32 + lane], a4[0]);
@@ -1722,13 +1801,18 @@ __global__ __launch_bounds__(256, WPC) void spg_ecc_persist_bwd_kernel(const Spg
         SPG_XP(2);
         if constexpr (MATRIX) {
           if (c0 == 0) {
+            // (one batch of LDS reads for all register-resident edges, products of rows u >= n skipped: see the forward kernel)
+            f32x4 g4[KMAX];
+#pragma unroll
+            for (int u = 0; u < KMAX; ++u) g4[u] = *reinterpret_cast<const f32x4*>(hs + u * 32 + 4 * (lane & 7));
+#pragma unroll
+            for (int u = 0; u < KMAX; ++u) asm volatile("" : "+v"(g4[u]));
 #pragma unroll
             for (int u = 0; u < KMAX; ++u) {
               if (u < n) {
-                const f32x4 g4 = *reinterpret_cast<const f32x4*>(hs + u * 32 + 4 * (lane & 7));
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
-                  pq[q] += spg_dot4(wc[u][q], g4);
+                  pq[q] += spg_dot4(wc[u][q], g4[u]);
               }
             }
           }
@@ -1743,9 +1827,14 @@ __global__ __launch_bounds__(256, WPC) void spg_ecc_persist_bwd_kernel(const Spg
           }
         } else if (lane < 32) {
           if (c0 == 0) {
+            float gv[KMAX];      // (the same batch; one value per edge)
+#pragma unroll
+            for (int u = 0; u < KMAX; ++u) gv[u] = hs[u * 32 + lane];
+#pragma unroll
+            for (int u = 0; u < KMAX; ++u) asm volatile("" : "+v"(gv[u]));
 #pragma unroll
             for (int u = 0; u < KMAX; ++u)
-              if (u < n) acc = fmaf(wv[u], hs[u * 32 + lane], acc);
+              if (u < n) acc = fmaf(wv[u], gv[u], acc);
           }
           for (int u = (c0 == 0 ? KMAX : 0); u < n; ++u) acc = fmaf(p.W[(long)eis[u] * 32 + lane], hs[u * 32 + lane], acc);
         }
@@ -1794,7 +1883,7 @@ __global__ __launch_bounds__(256, WPC) void spg_ecc_persist_bwd_kernel(const Spg
     GruFwdState stf;
     if (saved) spg_px_unpack_state(fq0, fq1, fq2, stf);
     float dh_acc, da;
-    spg_gru_backward_node<true, (WPC == 1 ? 8 : 2)>(p.gru, sw, sa, sh, sx, sd, lane, true, j, dH, o, dh_acc, da, &stf, saved, &cb);
+    spg_gru_backward_node<true, (WPC == 1 ? 24 : 16), (WPC == 1 ? 32 : 16)>(p.gru, sw, sa, sh, sx, sd, lane, true, j, dH, o, dh_acc, da, &stf, saved, &cb);
     SPG_XP(4);
     if (lane < 32) {
       dhdir = dh_acc;
