@@ -882,6 +882,34 @@ int spg_text_parse(const uint8_t* text, long n_bytes, const int64_t* line_start,
  * offset 0), 1 = SPG_TEXT_MAX_LINE; -1 otherwise */
 int spg_text_debug_layout(int which);
 
+/* ---- result text on the device (csrc/spg_format.hip; what the reference writes with numpy.savetxt(fmt='%d') in
+ * partition/write_Semantic3d.py and, through plyfile's text writer, with '%.18g' per record in the *2ply functions of
+ * partition/provider.py).  A table: n_cols (<= SPG_TEXT_MAX_COLS) columns over n_rows rows; HOST arrays
+ * columns [n_cols] (device pointers, aligned to their element), kinds [n_cols] (SPG_FORMAT_*) and strides [n_cols] (in elements,
+ * >= 0: column c of a row-major [n, 3] matrix is {base + c, 3}).  The text: the fields of a row joined by exactly one space, every
+ * row ended by '\n'.  U8 / I32 / U32 / I64 fields are '%d'; an F32 field is Python's '%.18g' % float(v) for every bit pattern: 18
+ * significant digits of the exact value rounded to nearest, ties to even, trailing zeros and a bare point removed, fixed
+ * notation for a decimal exponent in [-4, 18) and d[.ddd]e+-XX otherwise, 0 / -0 / inf / -inf / nan.  A field has at most 24 bytes.
+ * Two phases on the caller's scratch (spg_format_workspace_bytes(n_rows, n_cols)), because the byte count sizes the output:
+ * spg_format_measure -> row_start int64 [n_rows + 1] on the device, row r occupies [row_start[r], row_start[r + 1]).
+ * spg_format_write: total_bytes = row_start[n_rows] as the caller read it back; out uint8 [capacity], 8-byte aligned.
+ * capacity < total_bytes returns -1 (spg_last_error) before any launch: nothing is written.  No store is issued beyond
+ * row_start[r + 1] or the capacity, whatever row_start holds. */
+enum { SPG_FORMAT_U8 = 0, SPG_FORMAT_I32 = 1, SPG_FORMAT_U32 = 2, SPG_FORMAT_I64 = 3, SPG_FORMAT_F32 = 4, SPG_FORMAT_KINDS = 5 };
+size_t spg_format_workspace_bytes(long n_rows, int n_cols);
+int spg_format_measure(const void* const* columns, const int* kinds, const long* strides, int n_cols, long n_rows, int64_t* row_start,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int spg_format_write(const void* const* columns, const int* kinds, const long* strides, int n_cols, long n_rows,
+                     const int64_t* row_start, long total_bytes, uint8_t* out, long capacity, void* stream);
+/* test helper (host only, no device is touched): the field of one HOST value, by the function the kernels run -> out (at least
+ * 24 bytes, not terminated); returns its length, -1 for a bad argument */
+int spg_format_debug_field(int kind, const void* value, char* out);
+/* error2ply's colours (partition/provider.py:73-98): rgb uint8 [n, 3], labels / prediction int64 [n] -> out uint8 [n, 3]: rgb / 255
+ * -> colorsys.rgb_to_hsv -> hue 0.333333 where label == prediction or label == 0, else 0; saturation min(1, s + 0.3); value
+ * min(1, v + 0.1) -> colorsys.hsv_to_rgb -> * 255 truncated.  Float64 in the reference's operation order without contraction:
+ * equal to the Python loop for every input. */
+int spg_error_colours(const uint8_t* rgb, const int64_t* labels, const int64_t* prediction, long n, uint8_t* out, void* stream);
+
 /* ---- l0 cut pursuit (csrc/spg_cutpursuit.hip).  rowptr / inc / ends of spg_edgegraph_build.
  * spg_mincut: cap int64 [E], cost0 / cost1 int64 [n], every value in [0, 2^28) -> label uint8 [n] minimising sum_v cost_label(v) +
  * sum_e cap_e [label_u != label_v]; among the minimisers the one with the fewest ones (label 1 = the vertices that reach the sink in

@@ -197,6 +197,11 @@ SIGNATURES = {
     'spg_text_lines': (_i, [_p, _l, _l, _p, _p, _sz, _p]),
     'spg_text_parse': (_i, [_p, _l, _p, _l, _i, ctypes.POINTER(_i), _p, _p, _p, _p, _p]),
     'spg_text_debug_layout': (_i, [_i]),
+    'spg_format_workspace_bytes': (_sz, [_l, _i]),
+    'spg_format_measure': (_i, [ctypes.POINTER(_p), ctypes.POINTER(_i), ctypes.POINTER(_l), _i, _l, _p, _p, _sz, _p]),
+    'spg_format_write': (_i, [ctypes.POINTER(_p), ctypes.POINTER(_i), ctypes.POINTER(_l), _i, _l, _p, _l, _p, _l, _p]),
+    'spg_format_debug_field': (_i, [_i, _p, ctypes.c_char_p]),
+    'spg_error_colours': (_i, [_p, _p, _p, _l, _p, _p]),
     'spg_mincut_workspace_bytes': (_sz, [_l, _l]),
     'spg_mincut': (_i, [_p, _p, _p, _l, _l, _p, _p, _p, _l, _p, _p, _p, _sz, _p]),
     'spg_cp_accumulate': (_i, [_p, _p, _p, _l, _i, _l, _p, _p, _p]),

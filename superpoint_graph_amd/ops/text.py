@@ -1,4 +1,5 @@
-"""Raw cloud text parsed on the device, and the file reader that streams it there (csrc/spg_text.hip)."""
+"""Raw cloud text parsed on the device, and the file reader that streams it there (csrc/spg_text.hip); result text formatted on the
+device and error2ply's colours (csrc/spg_format.hip)."""
 from __future__ import annotations
 
 import ctypes
@@ -6,7 +7,7 @@ import ctypes
 import torch
 
 from .._lib import check, lib
-from ._core import _ptr, _req, _stream, _workspace
+from ._core import _int_vec, _on_gpu, _ptr, _req, _stream, _workspace
 
 
 # --------------------------------------------------------------------------------------------------
@@ -148,3 +149,84 @@ class CloudTextReader:
                     count -= self.rows
         if held is not None and next(int(t.shape[0]) for t in held if t is not None) > 0:
             yield tuple(held)
+
+
+# --------------------------------------------------------------------------------------------------
+# result text (csrc/spg_format.hip; numpy.savetxt and plyfile's text writer in the reference): DESIGN.md section 4.11k
+# --------------------------------------------------------------------------------------------------
+FORMAT_KINDS = {torch.uint8: 0, torch.int32: 1, torch.uint32: 2, torch.int64: 3, torch.float32: 4}      # SPG_FORMAT_* of include/spg_hip.h
+FORMAT_MAX_FIELD = {torch.uint8: 3, torch.int32: 11, torch.uint32: 10, torch.int64: 20, torch.float32: 24}      # bytes of the longest field
+
+
+def _format_columns(columns):
+    """columns -> (the 1-D views, n_rows): an entry is a device tensor [n] (any stride >= 0, e.g. a column of a matrix) or a
+    contiguous [n, k], which stands for its k columns."""
+    flat = []
+    for i, t in enumerate(columns):
+        name = f'columns[{i}]'
+        _on_gpu(t, name)
+        if t.dtype not in FORMAT_KINDS:
+            raise TypeError(f'{name} must be uint8, int32, uint32, int64 or float32, got {t.dtype}')
+        if t.dim() == 2:
+            _req(t, None, name)
+            flat += [t[:, j] for j in range(t.shape[1])]
+        elif t.dim() == 1:
+            _req(t[:1], None, name)                                    # (the device test; the stride is the column's own)
+            if t.stride(0) < 0:
+                raise ValueError(f'{name} must not have a negative stride')
+            flat.append(t)
+        else:
+            raise ValueError(f'{name} must be [n] or [n, k], got {tuple(t.shape)}')
+    if not 1 <= len(flat) <= TEXT_MAX_COLS:
+        raise ValueError(f'format_table: 1 ... {TEXT_MAX_COLS} columns expected, got {len(flat)}')
+    n = int(flat[0].shape[0])
+    if any(int(t.shape[0]) != n for t in flat):
+        raise ValueError(f'format_table: columns of different lengths {[int(t.shape[0]) for t in flat]}')
+    return flat, n
+
+
+def format_table_capacity(columns):
+    """An upper bound of the bytes format_table writes for these columns (every field at its longest)."""
+    flat, n = _format_columns(columns)
+    return n * sum(FORMAT_MAX_FIELD[t.dtype] + 1 for t in flat)
+
+
+def format_table(columns, out=None):
+    """A table as text, formatted on the device: columns (at most 16 once [n, k] entries are expanded, see _format_columns) ->
+    (bytes uint8 [total] on the device, row_start int64 [n + 1]): row r is bytes[row_start[r]:row_start[r + 1]], its fields joined
+    by one space and ended by '\n'.  uint8 / int32 / uint32 / int64 fields are '%d', float32 fields are Python's
+    '%.18g' % float(v) for every bit pattern -- the text numpy.savetxt writes with those formats (include/spg_hip.h).
+    out: a uint8 device buffer to write into (its first `total` bytes are returned as a view); one too small raises
+    RuntimeError before anything is written.  One host synchronisation: the total, which sizes the output."""
+    flat, n = _format_columns(columns)
+    if out is not None:
+        _req(out, torch.uint8, 'out')
+        if out.dim() != 1 or out.data_ptr() % 8:
+            raise ValueError('format_table: out must be one-dimensional and 8-byte aligned')
+    L, dev, st = lib(), flat[0].device, _stream()
+    nc = len(flat)
+    ptrs = (ctypes.c_void_p * nc)(*[t.data_ptr() for t in flat])
+    kinds = (ctypes.c_int * nc)(*[FORMAT_KINDS[t.dtype] for t in flat])
+    strides = (ctypes.c_long * nc)(*[int(t.stride(0)) for t in flat])
+    ws = _workspace(L.spg_format_workspace_bytes, n, nc, dev=dev)
+    row_start = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    check(L.spg_format_measure(ptrs, kinds, strides, nc, n, _ptr(row_start), _ptr(ws), ws.numel(), st), 'spg_format_measure')
+    total = int(row_start[n])
+    if out is None:
+        out = torch.empty(total, dtype=torch.uint8, device=dev)
+    check(L.spg_format_write(ptrs, kinds, strides, nc, n, _ptr(row_start), total, _ptr(out), int(out.numel()), st), 'spg_format_write')
+    return out[:total], row_start
+
+
+def error_colours(rgb, labels, prediction):
+    """error2ply's colours (partition/provider.py:73-98) on the device: rgb uint8 [n, 3], labels / prediction integer [n] ->
+    uint8 [n, 3], green hue where label == prediction or label == 0 and red elsewhere, saturation + 0.3 and value + 0.1 capped
+    at 1; float64 in colorsys's operation order, equal to the reference's Python loop for every input."""
+    _req(rgb, torch.uint8, 'rgb')
+    if rgb.dim() != 2 or rgb.shape[1] != 3:
+        raise ValueError(f'error_colours: rgb must be [n, 3], got {tuple(rgb.shape)}')
+    n = int(rgb.shape[0])
+    labels, prediction = _int_vec(labels, n, torch.int64, 'labels'), _int_vec(prediction, n, torch.int64, 'prediction')
+    out = torch.empty(n, 3, dtype=torch.uint8, device=rgb.device)
+    check(lib().spg_error_colours(_ptr(rgb), _ptr(labels), _ptr(prediction), n, _ptr(out), _stream()), 'spg_error_colours')
+    return out
